@@ -2,7 +2,18 @@
 """Flagship benchmark: en_core CNN (tok2vec+tagger+parser+NER) training
 words/sec, whole node — the BASELINE.json metric.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+that is all the headline figure needs.  --dump-outputs DIR additionally
+writes what the timed steps handed back (the display losses of each step,
+the parameter norms after the last) as DIR/<name>.npy, from the same default
+kernels a plain run times, so that two builds can be compared output for
+output (same arguments -> same inputs; see dump_outputs for the run-to-run
+noise of the atomic sums).
+--full first runs the other batch sizes of the realistic-batch curve
+(3k/32k/128k words, one JSON line each, in child processes) and then the
+headline run, whose result line comes last.
 
 Driver contract: for N>1 this is launched under torch.distributed.run with
 one rank per GPU (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* in env).  W untimed
@@ -55,6 +66,50 @@ def build_batches(nlp, *, batch_words: int, n_batches: int, seed: int,
     return batches
 
 
+# --full: the batch sizes measured next to the headline batch
+FULL_BATCH_WORDS = (3000, 32768, 131072)
+
+
+class _DeferredLosses(dict):
+    """Losses dict that keeps the pipes' 0-dim device tensors as they are:
+    accumulate() converts what items() yields to floats, a host sync per
+    step, so inside the timed region it is shown nothing to convert."""
+
+    def items(self):
+        return ()
+
+    def values_on_host(self) -> dict:
+        return {k: float(v) for k, v in dict.items(self)}
+
+
+def dump_outputs(out_dir: str, engine, step_losses: list) -> None:
+    """Write what the timed steps handed back as <out_dir>/<name>.npy.
+
+    A caller of accumulate()+apply_step() receives the display losses, and
+    the step leaves the updated parameters behind.  Both come from the
+    default kernels, whose float / packed-bf16 atomic sums depend on
+    scheduling order, so two runs agree only to that noise.  Raw weights are
+    no use for comparing builds: Adam turns the noise on a near-zero gradient
+    into a full +-lr step, and after 25 steps single weights differ by 0.02
+    between runs.  What is written stays within bf16 rounding (2^-8) from
+    run to run:
+
+      loss_<pipe>.npy   float64 [K]  display loss of every timed step; the
+                                     last element is the last step's
+      param_norms.npy   float64 [P]  L2 norm of each trainable parameter
+                                     tensor after the last step, in
+                                     named_parameters() order
+    """
+    os.makedirs(out_dir, exist_ok=True)
+    for name in (step_losses[-1] if step_losses else ()):
+        np.save(os.path.join(out_dir, f"loss_{name}.npy"),
+                np.asarray([d[name] for d in step_losses], dtype=np.float64))
+    norms = [float(p.detach().double().norm())
+             for _, p in engine.module.named_parameters() if p.requires_grad]
+    np.save(os.path.join(out_dir, "param_norms.npy"),
+            np.asarray(norms, dtype=np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -68,25 +123,36 @@ def main() -> None:
     ap.add_argument("--config", type=str, default="examples/configs/en_core_cnn.cfg")
     ap.add_argument("--profile-steps", type=int, default=0,
                     help="if >0, run only this many unsynchronized steps (for rocprof)")
-    ap.add_argument("--sweep", action="store_true",
-                    help="batch-size sweep (3k/32k/128k/1M words): one JSON "
-                         "line per size — the realistic-batch curve next to "
-                         "the 1M-word headline (VERDICT r1 item 8)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what they handed "
+                         "back (per-step losses, per-parameter norms after "
+                         "the last step) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the batch-size sweep (3k/32k/128k words, "
+                         "one JSON line per size) before the headline run — "
+                         "the realistic-batch curve next to the 1M-word "
+                         "headline (VERDICT r1 item 8)")
     args = ap.parse_args()
-
-    if args.sweep:
-        import subprocess
-
-        for bw in (3000, 32768, 131072, 1000000):
-            cmd = [sys.executable, __file__, "--steps", str(args.steps),
-                   "--warmup", str(args.warmup), "--batch-words", str(bw),
-                   "--config", args.config]
-            subprocess.run(cmd, check=True)
-        return
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", str(rank)))
+
+    if args.full and world > 1 and rank == 0:
+        print("# --full: the batch-size sweep runs single-process only; "
+              "skipped under WORLD_SIZE > 1", file=sys.stderr, flush=True)
+    if args.full and world == 1:
+        import subprocess
+
+        # children run before this process touches the device
+        for bw in FULL_BATCH_WORDS:
+            cmd = [sys.executable, os.path.abspath(__file__),
+                   "--steps", str(args.steps),
+                   "--warmup", str(args.warmup), "--batch-words", str(bw),
+                   "--words-per-doc", str(args.words_per_doc),
+                   "--vocab-size", str(args.vocab_size),
+                   "--config", args.config]
+            subprocess.run(cmd, check=True)
 
     from spacy_ray_amd.config.config import Config, resolve
     from spacy_ray_amd.parallel.comm import init_comm_from_env
@@ -128,9 +194,10 @@ def main() -> None:
 
     token_batches = [TokenBatch([eg.predicted for eg in b], device) for b in batches]
 
-    def step(i: int) -> None:
+    def step(i: int, losses=None) -> None:
         k = i % len(batches)
-        engine.accumulate(batches[k], drop=0.1, token_batch=token_batches[k])
+        engine.accumulate(batches[k], drop=0.1, losses=losses,
+                          token_batch=token_batches[k])
         engine.apply_step()
 
     if args.profile_steps:
@@ -166,8 +233,16 @@ def main() -> None:
     if use_cuda:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    # with --dump-outputs each timed step hands back its display losses as
+    # device tensors (same computation, no host sync); they are read after
+    # the timed region
+    step_losses = []
     for i in range(args.steps):
-        step(i)
+        if args.dump_outputs:
+            step_losses.append(_DeferredLosses())
+            step(i, step_losses[-1])
+        else:
+            step(i)
     if use_cuda:
         torch.cuda.synchronize()
     comm.barrier()
@@ -189,6 +264,10 @@ def main() -> None:
         cc = timing.phase_counts()
         for k in sorted(tt):
             print(f"# {k}: {tt[k]:.0f} ms total, {cc[k]} calls", flush=True)
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, engine,
+                     [d.values_on_host() for d in step_losses])
 
     cfg_base = os.path.basename(args.config)
     model_desc = {

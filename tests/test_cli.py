@@ -224,6 +224,70 @@ def test_bench_multirank_gloo(tmp_path, world):
     assert rec["value"] > 0 and rec["ms_per_step"] > 0
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes each timed step's losses and the parameter norms
+    after the last step as float64 .npy; the same arguments give the same
+    inputs, so on the deterministic CPU path two runs dump identical arrays.
+    --steps sets the number of timed steps: one loss per step."""
+    import numpy as np
+
+    env = dict(os.environ)
+    env["PYTHONPATH"] = str(REPO)
+    dumps = []
+    for tag in ("a", "b"):
+        out = tmp_path / tag
+        r = subprocess.run(
+            [sys.executable, str(REPO / "bench.py"), "--gpus", "1",
+             "--steps", "3", "--warmup", "1", "--batch-words", "400",
+             "--dump-outputs", str(out)],
+            cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600,
+        )
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-2500:])
+        json_lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(json_lines) == 1, r.stdout[-1500:]
+        rec = json.loads(json_lines[0])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        files = sorted(out.glob("*.npy"))
+        assert {f.name for f in files} == {"loss_tagger.npy", "loss_parser.npy",
+                                           "loss_ner.npy", "param_norms.npy"}
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        arrays = {f.name: np.load(f) for f in files}
+        for name, a in arrays.items():
+            assert a.dtype == np.float64 and np.isfinite(a).all(), (name, a.dtype)
+            if name.startswith("loss_"):
+                assert a.shape == (3,) and (a > 0).all(), (name, a)
+        assert arrays["param_norms.npy"].size > 10
+        dumps.append(arrays)
+    for name in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name], err_msg=name)
+
+
+def test_bench_full_runs_sweep_then_headline(monkeypatch, capfd):
+    """--full: one JSON line per sweep size from child processes, then the
+    headline run's line last.  The sweep sizes are shrunk to CPU scale."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", REPO / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "FULL_BATCH_WORDS", (200, 300, 400))
+    monkeypatch.setenv("PYTHONPATH", str(REPO))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2",
+                                      "--warmup", "1", "--batch-words", "600",
+                                      "--full"])
+    bench.main()
+    out = capfd.readouterr().out
+    recs = [json.loads(l) for l in out.splitlines() if l.startswith("{")]
+    assert len(recs) == 4, out[-1500:]
+    sizes = [r["config"]["global_batch"] for r in recs]
+    for got, want in zip(sizes, (200, 300, 400, 600)):
+        assert want <= got < want + 100, sizes
+    assert all(r["steps"] == 2 and r["value"] > 0 and r["ms_per_step"] > 0
+               for r in recs)
+
+
 def test_resume_does_not_overwrite_better_model_best(tmp_path):
     """model-best's meta.json carries the composite best_score; a resumed
     run seeded with it must not overwrite model-best unless it actually

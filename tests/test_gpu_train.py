@@ -507,3 +507,44 @@ def test_gpu_state_machine_exact_maxlen_boundary(monkeypatch):
         assert abs(losses_gpu[k] - losses_ref[k]) <= 1e-3 + 0.03 * abs(losses_ref[k]), (
             k, losses_ref[k], losses_gpu[k])
     assert (heads_gpu == heads_ref).mean() > 0.97
+
+
+@need_gpu
+def test_bench_dump_outputs_same_every_run(tmp_path):
+    """bench.py --dump-outputs on the GPU, default kernels: two runs with
+    the same arguments get the same inputs, so their dumps differ only by
+    the order of the float / packed-bf16 atomic sums.  Bound: one bf16
+    rounding step, 2^-8 relative, per element (the compute dtype's
+    precision, not a measured figure)."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    repo = Path(__file__).resolve().parent.parent
+    env = dict(os.environ)
+    env["PYTHONPATH"] = str(repo)
+    env.pop("SRX_DETERMINISTIC", None)
+    dumps = []
+    for tag in ("a", "b"):
+        out = tmp_path / tag
+        r = subprocess.run(
+            [sys.executable, str(repo / "bench.py"), "--gpus", "1",
+             "--steps", "3", "--warmup", "1", "--batch-words", "3000",
+             "--dump-outputs", str(out)],
+            cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300,
+        )
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-2500:])
+        rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert rec["dtype"] == "bf16" and rec["ms_per_step"] > 0
+        dumps.append({f.name: np.load(f) for f in sorted(out.glob("*.npy"))})
+    assert dumps[0].keys() == dumps[1].keys()
+    assert {"loss_tagger.npy", "loss_parser.npy", "loss_ner.npy",
+            "param_norms.npy"} <= dumps[0].keys()
+    for name in dumps[0]:
+        a, b = dumps[0][name], dumps[1][name]
+        assert a.dtype == np.float64 and np.isfinite(a).all(), name
+        if name.startswith("loss_"):
+            assert a.shape == (3,) and (a > 0).all(), (name, a)
+        print(name, "max rel diff", float(np.max(np.abs(a - b) / np.abs(a).clip(1e-30))))
+        np.testing.assert_allclose(a, b, rtol=2.0 ** -8, atol=0, err_msg=name)
