@@ -844,9 +844,12 @@ class _WindowAttention(torch.autograd.Function):
     def forward(ctx, q, k, v, lens, scale, drop_p):
         hip = hip_ext()
         B, H, L, D = q.shape
-        qf = q.reshape(B * H, L, D)
-        kf = k.reshape(B * H, L, D)
-        vf = v.reshape(B * H, L, D)
+        # .contiguous(): for B == 1 the reshape of a transposed [B, L, H, D]
+        # operand is a strided VIEW and the kernels index raw pointers
+        # (no copy when the reshape already produced a dense tensor)
+        qf = q.reshape(B * H, L, D).contiguous()
+        kf = k.reshape(B * H, L, D).contiguous()
+        vf = v.reshape(B * H, L, D).contiguous()
         seed = (int(torch.randint(0, 2**62, (1,), device="cpu").item())
                 if drop_p > 0 else 0)
         fused = (L <= 96 and D == 64 and q.dtype == torch.bfloat16

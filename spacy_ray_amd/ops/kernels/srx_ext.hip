@@ -656,6 +656,32 @@ at::Tensor act_bwd(at::Tensor dY, at::Tensor X, int64_t op, double slope,
 // ----------------------------------------------------- attention softmax
 // Fused masked softmax (+dropout) between the two attention bmm GEMMs —
 // srx_attn.hip.h.  S/P/dS: [NH, L, L]; lens: [NH/heads] int32.
+// Shared argument guards of the attention launchers: the kernels index raw
+// pointers, so every operand must be a dense GPU tensor of the expected
+// dtype and lens must hold exactly one int32 per window.
+static void check_attn_lens(const at::Tensor& lens, long NH, int64_t heads) {
+  TORCH_CHECK(lens.is_cuda() && lens.is_contiguous(),
+              "attention: lens must be a contiguous GPU tensor");
+  TORCH_CHECK(lens.scalar_type() == at::kInt, "attention: lens must be int32");
+  TORCH_CHECK(heads > 0 && NH % heads == 0 && lens.numel() == NH / heads,
+              "attention: lens must have NH / heads entries");
+}
+
+static void check_attn_like(const at::Tensor& t, const at::Tensor& ref,
+                            const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), what,
+              ": expected a contiguous GPU tensor");
+  TORCH_CHECK(t.scalar_type() == ref.scalar_type() && t.sizes() == ref.sizes(),
+              what, ": dtype/shape mismatch");
+}
+
+static void check_attn_lse(const at::Tensor& lse, long NH, int L) {
+  TORCH_CHECK(lse.is_cuda() && lse.is_contiguous() &&
+                  lse.scalar_type() == at::kFloat && lse.dim() == 2 &&
+                  lse.size(0) == NH && lse.size(1) == L,
+              "attention: lse must be a contiguous fp32 [NH, L] GPU tensor");
+}
+
 std::vector<at::Tensor> attn_softmax_fwd(at::Tensor S, at::Tensor lens,
                                          int64_t heads, double scale,
                                          double drop_p, int64_t seed) {
@@ -663,6 +689,8 @@ std::vector<at::Tensor> attn_softmax_fwd(at::Tensor S, at::Tensor lens,
   long NH = S.size(0);
   int L = (int)S.size(-1);
   TORCH_CHECK(L <= SRX_ATTN_MAX_L, "attn softmax: L <= 256");
+  TORCH_CHECK(S.dim() == 3 && S.size(1) == L, "attn softmax: S must be [NH, L, L]");
+  check_attn_lens(lens, NH, heads);
   auto P = at::empty_like(S);
   auto lse = at::empty({NH, (long)L}, S.options().dtype(at::kFloat));
   long n_rows = NH * L;
@@ -695,6 +723,11 @@ at::Tensor attn_softmax_bwd(at::Tensor S, at::Tensor lse, at::Tensor dPt,
   check_dev(S);
   long NH = S.size(0);
   int L = (int)S.size(-1);
+  TORCH_CHECK(L <= SRX_ATTN_MAX_L, "attn softmax: L <= 256");
+  TORCH_CHECK(S.dim() == 3 && S.size(1) == L, "attn softmax: S must be [NH, L, L]");
+  check_attn_like(dPt, S, "attn softmax dP");
+  check_attn_lse(lse, NH, L);
+  check_attn_lens(lens, NH, heads);
   auto dS = at::empty_like(S);
   long n_rows = NH * L;
   if (n_rows == 0) return dS;
@@ -733,6 +766,10 @@ std::vector<at::Tensor> attn_fused_fwd(at::Tensor Q, at::Tensor K,
   int L = (int)Q.size(1);
   TORCH_CHECK((int)Q.size(2) == 64, "fused attention needs D == 64");
   TORCH_CHECK(L <= SRX_ATTN_FUSED_MAX_L, "fused attention: L <= 96");
+  TORCH_CHECK(Q.dim() == 3, "fused attention: Q must be [NH, L, 64]");
+  check_attn_like(K, Q, "fused attention K");
+  check_attn_like(V, Q, "fused attention V");
+  check_attn_lens(lens, NH, heads);
   auto O = at::empty_like(Q);
   auto lse = at::empty({NH, (long)L}, Q.options().dtype(at::kFloat));
   if (NH == 0) return {O, lse};
@@ -775,8 +812,16 @@ std::vector<at::Tensor> attn_fused_bwd(at::Tensor Q, at::Tensor K,
                                        int64_t heads, double scale,
                                        double drop_p, int64_t seed) {
   check_dev(Q);
+  TORCH_CHECK(Q.scalar_type() == at::kBFloat16, "fused attention is bf16-only");
+  TORCH_CHECK(Q.dim() == 3 && Q.size(2) == 64, "fused attention needs D == 64");
   long NH = Q.size(0);
   int L = (int)Q.size(1);
+  TORCH_CHECK(L <= SRX_ATTN_FUSED_MAX_L, "fused attention: L <= 96");
+  check_attn_like(K, Q, "fused attention K");
+  check_attn_like(V, Q, "fused attention V");
+  check_attn_like(dO, Q, "fused attention dO");
+  check_attn_lse(lse, NH, L);
+  check_attn_lens(lens, NH, heads);
   auto dQ = at::empty_like(Q);
   auto dK = at::empty_like(Q);
   auto dV = at::empty_like(Q);
