@@ -560,9 +560,9 @@ def parser_scatter_entries(entries, dPre32) -> None:
 class _MWELayer(torch.autograd.Function):
     """One MaxoutWindowEncoder block as a single hand-written MFMA kernel:
     Y = X + LN(maxout_3(seq2col(X) @ W^T + bias)).  Forward is the fused
-    gfx950 kernel (srx_mwe.hip.h); backward composes existing kernels:
-    layernorm_bwd on the saved maxout output -> maxout scatter -> the two
-    GEMM backwards (hipBLASLt) with seq2col recomputed -> seq2col_bwd."""
+    gfx950 kernel (srx_mwe.hip.h); backward: fused stage 1 (mask x
+    layernorm_bwd x maxout scatter) -> dW GEMM (hipBLASLt) with seq2col
+    recomputed -> fused dX kernel (dPre @ W, seq2col_bwd and the residual)."""
 
     @staticmethod
     def forward(ctx, X, weight, bias, g, b, starts, ends, dropmask, eps):
@@ -590,9 +590,8 @@ class _MWELayer(torch.autograd.Function):
         # GEMM backwards (pre = X3 @ W^T)
         X3 = hip.seq2col_fwd(X, starts, ends)
         dW = mm_dw_chunked(dPre, X3)
-        dX3 = dPre.mm(weight)
-        # seq2col backward with the residual dY folded in
-        dX = hip.seq2col_bwd(dX3.contiguous(), starts, ends, dY)
+        # dX = dY + seq2col_bwd(dPre @ weight), fused (no [T,3W] product)
+        dX = hip.mwe_bwd_dx(dPre, weight, starts, ends, dY)
         return (dX, dW, dbias32.to(dY.dtype), dg32.to(dY.dtype),
                 db32.to(dY.dtype), None, None, None, None)
 

@@ -1031,12 +1031,12 @@ void launch_mwe(const at::Tensor& X, const at::Tensor& Wt, const at::Tensor& bia
                 at::Tensor& Y, at::Tensor& Mout,
                 at::Tensor& which, at::Tensor& mu, at::Tensor& rstd, long T,
                 double eps, hipStream_t stream) {
-  constexpr int WP = W + 8;
-  constexpr int NW = W / 32;
-  // per-section staging: [64][WP] A + [3W][WP] B (73 KB at W=96 -> two
-  // blocks per CU; the old all-sections layout was 101 KB -> one block)
-  size_t lds_bytes = (size_t)(64 * WP + 3 * W * WP) * sizeof(bf16_t) +
-                     (size_t)(2 * NW * 64) * sizeof(float);
+  using C = MweCfg<W, false>;
+  // X halo image + double-buffered B chunks + LN partials / row stats
+  // (77 KB at W=96 -> two 6-wave workgroups per CU; 102 KB at W=128 -> one
+  // 8-wave workgroup)
+  size_t lds_bytes = (size_t)(C::A_ELEMS + C::B_ELEMS) * sizeof(bf16_t) +
+                     (size_t)(2 * C::NW * C::MT + 2 * C::MT) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)mwe_layer_fwd_kernel<W>,
@@ -1044,8 +1044,8 @@ void launch_mwe(const at::Tensor& X, const at::Tensor& Wt, const at::Tensor& bia
                               (int)lds_bytes);
     attr_set = true;
   }
-  dim3 grid((unsigned)(T / 64));
-  hipLaunchKernelGGL((mwe_layer_fwd_kernel<W>), grid, dim3(64 * NW), lds_bytes,
+  dim3 grid((unsigned)((T + C::MT - 1) / C::MT));
+  hipLaunchKernelGGL((mwe_layer_fwd_kernel<W>), grid, dim3(C::NT), lds_bytes,
                      stream, (const bf16_t*)X.data_ptr(), (const bf16_t*)Wt.data_ptr(),
                      (const bf16_t*)bias.data_ptr(), (const bf16_t*)g.data_ptr(),
                      (const bf16_t*)b.data_ptr(), starts.data_ptr<uint8_t>(),
@@ -1082,6 +1082,64 @@ std::vector<at::Tensor> mwe_layer_fwd(at::Tensor X, at::Tensor Wt, at::Tensor bi
                       rstd, T, eps, stream);
   }
   return {Y, Mout, which, mu, rstd};
+}
+
+// ------------------------------------------------ fused MWE backward dX
+template <int W>
+void launch_mwe_bwd_dx(const at::Tensor& dPre, const at::Tensor& WT,
+                       const at::Tensor& starts, const at::Tensor& ends,
+                       const at::Tensor& dY, at::Tensor& dX, long T,
+                       hipStream_t stream) {
+  using C = MweCfg<W, true>;
+  // dPre halo image (K = 3W) + double-buffered B chunks: 117 KB at W=96,
+  // 152 KB at W=128 -> one workgroup per CU
+  size_t lds_bytes = (size_t)(C::A_ELEMS + C::B_ELEMS) * sizeof(bf16_t);
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)mwe_bwd_dx_kernel<W>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_bytes);
+    attr_set = true;
+  }
+  dim3 grid((unsigned)((T + C::MT - 1) / C::MT));
+  hipLaunchKernelGGL((mwe_bwd_dx_kernel<W>), grid, dim3(C::NT), lds_bytes, stream,
+                     (const bf16_t*)dPre.data_ptr(), (const bf16_t*)WT.data_ptr(),
+                     starts.data_ptr<uint8_t>(), ends.data_ptr<uint8_t>(),
+                     (const bf16_t*)dY.data_ptr(), (bf16_t*)dX.data_ptr(), T);
+}
+
+// dX = dY + seq2col_bwd(dPre @ weight) in one kernel (no [T,3W] product,
+// no atomics); see mwe_bwd_dx_kernel.
+at::Tensor mwe_bwd_dx(at::Tensor dPre, at::Tensor weight, at::Tensor starts,
+                      at::Tensor ends, at::Tensor dY) {
+  check_dev(dPre);
+  check_dev(dY);
+  TORCH_CHECK(weight.is_cuda(), "expected a GPU tensor");
+  TORCH_CHECK(dPre.scalar_type() == at::kBFloat16 &&
+                  weight.scalar_type() == at::kBFloat16 &&
+                  dY.scalar_type() == at::kBFloat16,
+              "mwe_bwd_dx is bf16-only");
+  TORCH_CHECK(dPre.dim() == 2 && dY.dim() == 2 && weight.dim() == 2,
+              "mwe_bwd_dx expects 2-d tensors");
+  long T = dY.size(0);
+  int W = (int)dY.size(1);
+  TORCH_CHECK(W == 96 || W == 128, "mwe_bwd_dx supports W in {96,128}");
+  TORCH_CHECK(T % 64 == 0, "mwe_bwd_dx needs T % 64 == 0 (TokenBatch pads)");
+  TORCH_CHECK(dPre.size(0) == T && dPre.size(1) == 3 * W, "dPre must be [T,3W]");
+  TORCH_CHECK(weight.size(0) == 3 * W && weight.size(1) == 3 * W,
+              "weight must be [3W,3W]");
+  TORCH_CHECK(starts.numel() == T && ends.numel() == T,
+              "starts/ends must have T entries");
+  auto dX = at::empty_like(dY);
+  if (T == 0) return dX;
+  // k-contiguous B rows: section s, output column n -> WT[sW + n, :]
+  auto WT = weight.t().contiguous();
+  auto stream = at::cuda::getCurrentCUDAStream();
+  if (W == 96)
+    launch_mwe_bwd_dx<96>(dPre, WT, starts, ends, dY, dX, T, stream);
+  else
+    launch_mwe_bwd_dx<128>(dPre, WT, starts, ends, dY, dX, T, stream);
+  return dX;
 }
 
 // --------------------------------------------- fused transition step (C++)
@@ -1223,6 +1281,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("reduce_ragged_bwd", &reduce_ragged_bwd);
   m.def("reduce_max_bwd", &reduce_max_bwd);
   m.def("mwe_layer_fwd", &mwe_layer_fwd);
+  m.def("mwe_bwd_dx", &mwe_bwd_dx, py::arg("dPre"), py::arg("weight"),
+        py::arg("starts"), py::arg("ends"), py::arg("dY"));
   m.def("fused_step", &fusedstep::fused_step);
   m.def("fused_entries_take", &fusedstep::fused_entries_take);
   m.def("transition_ce", &transition_ce, py::arg("scores"), py::arg("gold"),

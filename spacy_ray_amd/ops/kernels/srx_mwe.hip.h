@@ -1,42 +1,244 @@
 // Fused MaxoutWindowEncoder layer (SURVEY.md §2.5 `mwe_layer`):
 //   Y = X + LayerNorm(maxout_{P=3}(seq2col_{win=1}(X) @ Wt^T + bias))
-// in ONE kernel launch — hand-written MFMA (v_mfma_f32_32x32x16_bf16) with
-// LDS-tiled operands.
+// in ONE kernel launch, and the matching backward dX
+//   dX[t] = dY[t] + sum_s m_s(t) * dPre[t+1-s] @ weight[:, sW:(s+1)W]
+// also in one launch — hand-written MFMA (v_mfma_f32_32x32x16_bf16) with
+// LDS-tiled operands.  Both are the same "3 shifted sections" GEMM and
+// share the tile machinery below (MweCfg / mwe_tile_gemm).
 //
-// Geometry (gfx950), W = 96 or 128:
-// * block = W/32 waves (192 / 256 threads), one 64-token M-tile per block;
-// * K = 3W decomposes into the 3 window sections: section s multiplies
-//   A_s = X[t-1+s] (doc-boundary-zeroed) by B_s = cols [sW,(s+1)W) of the
-//   weight — seq2col is never materialized;
-// * wave w owns within-piece 32-col tile position w for ALL 3 pieces
+// Tile machinery (gfx950), W = 96 or 128:
+// * one 128-row M tile per workgroup, 2 * W/32 waves (384 / 512 threads):
+//   wave (mh, w) owns rows [64 mh, 64 mh + 64) and the 32-col tile position
+//   w.  In the forward that is within-piece position w of ALL 3 pieces
 //   (global n-tile p*(W/32)+w): the P=3 maxout is an in-register
-//   elementwise max over the wave's own 3 accumulators, and the LayerNorm
-//   column span of a wave is exactly within-piece cols [32w, 32w+32);
-// * A and B are staged PER SECTION ([64][W+8] + [3W][W+8] at a time, not
-//   all three sections at once): at W=96 that is 73 KB of LDS instead of
-//   101 KB, which fits TWO blocks per CU (6 waves) instead of one — MFMA
-//   and staging latency of one block hides under the other (the
-//   single-block version measured 1.85 ms at T=1M; occupancy was the
-//   bound, not bandwidth: the 166 KB weight re-read per block stays in
-//   L2).  +8 bf16 row pad: the natural 48/64-dword stride would
-//   multi-way-conflict ds_read_b128; 52/68 dwords pad to 2-way;
-// * B section staged TRANSPOSED in LDS [3W][W+8] so a lane's 8 consecutive
-//   k-elements are contiguous (ds_read_b128);
-// * LayerNorm row stats: 5-step __shfl_xor column reduce per wave -> LDS
-//   partials -> combine across waves; epilogue adds the residual re-read
-//   from global X (hot in L2).
+//   elementwise max over the wave's own 3 accumulators;
+// * the A operand (X, or dPre with K = 3W) is staged ONCE as a halo image,
+//   rows t0-1 .. t0+128, by all threads with 16-byte coalesced accesses.
+//   Section s reads it at row offset s (forward) or 2-s (backward).  The
+//   doc-boundary zeroing is per (row, section), so it is applied to the A
+//   fragment in registers (a v_cndmask on 4 VGPRs), never to the image;
+// * the B operand is streamed in K chunks ([3W][32] forward, [W][96]
+//   backward; rows are k-contiguous so a lane's 8 k-elements are one
+//   ds_read_b128), double-buffered in LDS with a register prefetch: the
+//   global loads of chunk c+1 are issued before the MFMAs of chunk c and
+//   written to the other buffer after them — one barrier per chunk, 12
+//   MFMAs per wave between barriers.  The weight is staged once per 128
+//   rows (was once per 64);
+// * +8 bf16 row pad on every image: strides of 20 / 52 / 68 / 148 / 196
+//   dwords put 16 consecutive rows on 16 distinct 4-bank slots, which is
+//   conflict-free for ds_read_b128's 16-lane groups.
 //
-// Saved for the composed backward: maxout output M, argmax, mu, rstd
-// (backward = layernorm_bwd + maxout scatter + two GEMMs + seq2col_bwd,
-// all existing kernels/hipBLASLt).
+// Forward epilogue: maxout in fp32 on the accumulators; LayerNorm row sums
+// by a halving butterfly (lanes swap half of their 16 row values per step:
+// 16 shuffles per quantity instead of 80), partials combined through LDS,
+// mu / rstd computed once per row.  The dropmask tile is staged into the
+// (now free) B region with 16-byte loads; the residual comes from the
+// staged X image; Y overwrites the X image, Mout the mask tile, `which`
+// its own tile, and all three leave with 16-byte row-contiguous stores.
+//
+// Compiler resource report (hipcc -Rpass-analysis=kernel-resource-usage,
+// gfx950; AGPR 0 and scratch 0 in all four):
+//   mwe_layer_fwd_kernel<96>   147 VGPR  LDS  77,216 B  2 workgroups (12 waves) / CU
+//   mwe_layer_fwd_kernel<128>  149 VGPR  LDS 101,920 B  1 workgroup  ( 8 waves) / CU
+//   mwe_bwd_dx_kernel<96>      113 VGPR  LDS 116,896 B  1 workgroup  ( 6 waves) / CU
+//   mwe_bwd_dx_kernel<128>     126 VGPR  LDS 155,168 B  1 workgroup  ( 8 waves) / CU
+// Measured at T=1M, W=96 (MI355X): forward 1.32 -> 0.54 ms, dX 0.77
+// (GEMM + seq2col_bwd) -> 0.47 ms; see profiles/README.md.
+//
+// Saved for the backward: maxout output M, argmax, mu, rstd (backward =
+// mwe_bwd_stage1 + recomputed seq2col + dW GEMM + mwe_bwd_dx).
 #pragma once
 #include "srx_common.hip.h"
 
 typedef __attribute__((__vector_size__(8 * sizeof(short)))) short srx_bf16x8;
 typedef __attribute__((__vector_size__(16 * sizeof(float)))) float srx_f32x16;
 
+// ---------------------------------------------------- shared tile machinery
+template <int W_, bool BWD_>
+struct MweCfg {
+  static constexpr int W = W_;
+  static constexpr bool BWD = BWD_;
+  static constexpr int NW = W / 32;            // 32-col tile positions
+  static constexpr int MT = 128;               // rows per workgroup
+  static constexpr int NT = 64 * 2 * NW;       // threads = 4 W
+  static constexpr int KA = BWD ? 3 * W : W;   // A row length = K per section
+  static constexpr int AP = KA + 8;            // padded A image row (bf16)
+  static constexpr int KC = BWD ? 96 : 32;     // K chunk of the B stream
+  static constexpr int BP = KC + 8;            // padded B chunk row (bf16)
+  static constexpr int NBR = BWD ? W : 3 * W;  // B rows per chunk
+  static constexpr int NP = BWD ? 1 : 3;       // accumulator tiles per wave / 2
+  static constexpr int CPS = KA / KC;          // chunks per section
+  static constexpr int NC = 3 * CPS;
+  static constexpr int PF = NBR * (KC / 8) / NT;  // 16-byte pieces per thread
+  static constexpr int A_ROWS = MT + 2;
+  static constexpr int A_ELEMS = A_ROWS * AP;
+  static constexpr int B_ELEMS = 2 * NBR * BP;
+  static constexpr int A_ITERS = (A_ROWS * (KA / 8) + NT - 1) / NT;
+  static_assert(KA % KC == 0, "K chunking");
+  static_assert(PF * NT == NBR * (KC / 8), "B chunk must split evenly");
+};
+
+// global -> registers: this thread's pieces of B chunk c
+template <class C>
+__device__ __forceinline__ void mwe_b_fetch(const bf16_t* __restrict__ Bm, int c,
+                                            int tid, srx_u32x4_t (&pf)[C::PF]) {
+  const int s = c / C::CPS, kc = c % C::CPS;
+  const int rowbase = C::BWD ? s * C::W : 0;
+  const int coloff = (C::BWD ? 0 : s * C::W) + kc * C::KC;
+#pragma unroll
+  for (int i = 0; i < C::PF; i++) {
+    const int id = i * C::NT + tid;
+    const int j = id / (C::KC / 8), q = id % (C::KC / 8);
+    pf[i] = *(const srx_u32x4_t*)(Bm + (long)(rowbase + j) * (3 * C::W) +
+                                  coloff + q * 8);
+  }
+}
+
+template <class C>
+__device__ __forceinline__ void mwe_b_store(bf16_t* ldsBbuf, int tid,
+                                            const srx_u32x4_t (&pf)[C::PF]) {
+#pragma unroll
+  for (int i = 0; i < C::PF; i++) {
+    const int id = i * C::NT + tid;
+    const int j = id / (C::KC / 8), q = id % (C::KC / 8);
+    *(srx_u32x4_t*)(ldsBbuf + j * C::BP + q * 8) = pf[i];
+  }
+}
+
+// acc[p][mi] (+)= sum over the 3 sections of mask_s(row) * A[row + shift_s]
+// times B_s, for this wave's rows [64 mh + 32 mi, +32) and B rows
+// 32 (p NW + w) + [0, 32).  A is [T, KA]; image row i holds A[t0 - 1 + i]
+// (zero outside [0, T)).  Section s of the forward multiplies A[t - 1 + s]
+// by Bm[:, sW + k] and is dropped for s=0 at a doc start / t=0 and for s=2
+// at a doc end / t=T-1; section s of the backward multiplies A[t + 1 - s]
+// by Bm[sW + n, k] and is dropped for s=0 when t+1 starts a doc / is T and
+// for s=2 when t-1 ends a doc / t=0 (the masks of seq2col_bwd_kernel).
+// Ends with a barrier: both LDS regions are free afterwards.
+template <class C>
+__device__ __forceinline__ void mwe_tile_gemm(
+    const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm,
+    const uint8_t* __restrict__ is_start, const uint8_t* __restrict__ is_end,
+    long T, long t0, bf16_t* ldsA, bf16_t* ldsB,
+    srx_f32x16 (&acc)[C::NP][2]) {
+  const int tid = threadIdx.x;
+  const int lane = tid % SRX_WAVE;
+  const int wave = tid / SRX_WAVE;
+  const int mh = wave / C::NW, w = wave % C::NW;
+
+#pragma unroll
+  for (int p = 0; p < C::NP; p++)
+#pragma unroll
+    for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+      for (int rr = 0; rr < 16; rr++) acc[p][mi][rr] = 0.f;
+
+  srx_u32x4_t pf[C::PF];
+  mwe_b_fetch<C>(Bm, 0, tid, pf);
+
+  // A halo image: all loads first, then all LDS writes
+  {
+    srx_u32x4_t v[C::A_ITERS];
+#pragma unroll
+    for (int it = 0; it < C::A_ITERS; it++) {
+      const int id = it * C::NT + tid;
+      const int i = id / (C::KA / 8), q = id % (C::KA / 8);
+      const long t = t0 - 1 + i;
+      v[it] = srx_u32x4_t{0u, 0u, 0u, 0u};
+      if (i < C::A_ROWS && t >= 0 && t < T)
+        v[it] = *(const srx_u32x4_t*)(A + t * C::KA + q * 8);
+    }
+#pragma unroll
+    for (int it = 0; it < C::A_ITERS; it++) {
+      const int id = it * C::NT + tid;
+      const int i = id / (C::KA / 8), q = id % (C::KA / 8);
+      if (i < C::A_ROWS) *(srx_u32x4_t*)(ldsA + i * C::AP + q * 8) = v[it];
+    }
+  }
+
+  // per-lane section masks of its two A rows: bit s set = section s is zero
+  int zmask[2];
+#pragma unroll
+  for (int mi = 0; mi < 2; mi++) {
+    const long t = t0 + 64 * mh + 32 * mi + (lane & 31);
+    int z = 7;
+    if (t < T) {
+      bool z0, z2;
+      if (C::BWD) {
+        z0 = (t + 1 >= T) || is_start[t + 1];
+        z2 = (t == 0) || is_end[t - 1];
+      } else {
+        z0 = (t == 0) || is_start[t];
+        z2 = (t == T - 1) || is_end[t];
+      }
+      z = (z0 ? 1 : 0) | (z2 ? 4 : 0);
+    }
+    zmask[mi] = z;
+  }
+
+  mwe_b_store<C>(ldsB, tid, pf);
+  __syncthreads();
+
+  for (int c = 0; c < C::NC; c++) {
+    if (c + 1 < C::NC) mwe_b_fetch<C>(Bm, c + 1, tid, pf);
+    const int s = c / C::CPS, kc = c % C::CPS;
+    const bf16_t* bbuf = ldsB + (c & 1) * (C::NBR * C::BP);
+    const int arow = 64 * mh + (lane & 31) + (C::BWD ? 2 - s : s);
+    const bf16_t* abase = ldsA + arow * C::AP + kc * C::KC + 8 * (lane >> 5);
+    const bf16_t* bbase = bbuf + (32 * w + (lane & 31)) * C::BP + 8 * (lane >> 5);
+    const bool zr0 = (zmask[0] >> s) & 1, zr1 = (zmask[1] >> s) & 1;
+#pragma unroll
+    for (int ks = 0; ks < C::KC / 16; ks++) {
+      // A fragment (32x32x16 bf16): lane holds A[row (lane&31)]
+      // [k + 8*(lane>>5) + e], e=0..7 — one ds_read_b128
+      srx_bf16x8 afrag[2];
+      afrag[0] = *(const srx_bf16x8*)(abase + ks * 16);
+      afrag[1] = *(const srx_bf16x8*)(abase + 32 * C::AP + ks * 16);
+      const srx_bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (zr0) afrag[0] = zero;
+      if (zr1) afrag[1] = zero;
+#pragma unroll
+      for (int p = 0; p < C::NP; p++) {
+        srx_bf16x8 bfrag =
+            *(const srx_bf16x8*)(bbase + p * (32 * C::NW) * C::BP + ks * 16);
+#pragma unroll
+        for (int mi = 0; mi < 2; mi++)
+          acc[p][mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              afrag[mi], bfrag, acc[p][mi], 0, 0, 0);
+      }
+    }
+    if (c + 1 < C::NC)
+      mwe_b_store<C>(ldsB + ((c + 1) & 1) * (C::NBR * C::BP), tid, pf);
+    __syncthreads();
+  }
+}
+
+// One halving step of the row-sum butterfly: the lane keeps the half of
+// its N values selected by bit `BIT` of its id, sends the other half to
+// lane ^ (1 << BIT) and adds what it receives.  After steps 16, 8, 4, 2 on
+// bits 0..3, v[0] is the sum over 16 lanes of the value with index
+// 8 b0 + 4 b1 + 2 b2 + b3 (b_i = bit i of the lane id).
+template <int N, int BIT>
+__device__ __forceinline__ void mwe_fold(float (&v)[16], int lane) {
+  const bool hi = (lane >> BIT) & 1;
+#pragma unroll
+  for (int i = 0; i < N / 2; i++) {
+    const float keep = hi ? v[i + N / 2] : v[i];
+    const float send = hi ? v[i] : v[i + N / 2];
+    v[i] = keep + __shfl_xor(send, 1 << BIT, SRX_WAVE);
+  }
+}
+
+__device__ __forceinline__ float mwe_row_sums(float (&v)[16], int lane) {
+  mwe_fold<16, 0>(v, lane);
+  mwe_fold<8, 1>(v, lane);
+  mwe_fold<4, 2>(v, lane);
+  mwe_fold<2, 3>(v, lane);
+  return v[0] + __shfl_xor(v[0], 16, SRX_WAVE);
+}
+
+// -------------------------------------------------------------- forward
 template <int W>
-__global__ __launch_bounds__(2 * W) void mwe_layer_fwd_kernel(
+__global__ __launch_bounds__(4 * W) void mwe_layer_fwd_kernel(
     const bf16_t* __restrict__ X,      // [T, W]
     const bf16_t* __restrict__ Wt,     // [3W (out, pieces-major), 3W (in)] row-major
     const bf16_t* __restrict__ bias,   // [3W]
@@ -51,88 +253,46 @@ __global__ __launch_bounds__(2 * W) void mwe_layer_fwd_kernel(
     float* __restrict__ mu_out,        // [T]
     float* __restrict__ rstd_out,      // [T]
     long T, float eps) {
-  constexpr int WP = W + 8;       // padded LDS row stride (bf16 elements)
-  constexpr int NW = W / 32;      // waves per block = within-piece tiles
-  extern __shared__ bf16_t lds[];
-  bf16_t* ldsA = lds;                          // 64 * WP (current section)
-  bf16_t* ldsB = lds + 64 * WP;                // 3W * WP (current section)
-  float* ldsP = (float*)(ldsB + 3 * W * WP);   // LN partials [2][NW][64]
+  using C = MweCfg<W, false>;
+  constexpr int WP = C::AP, NW = C::NW, MT = C::MT, NT = C::NT;
+  constexpr int WHP = W + 16;  // `which` tile row stride (bytes)
+  static_assert(MT * WP * 2 + MT * WHP <= C::B_ELEMS * 2, "epilogue tiles");
+  extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
+  bf16_t* ldsA = lds;                               // X halo image, then Y
+  bf16_t* ldsB = lds + C::A_ELEMS;                  // B chunks x2
+  bf16_t* ldsM = ldsB;                              // epilogue: mask, then Mout
+  uint8_t* ldsWh = (uint8_t*)(ldsB + MT * WP);      // epilogue: which
+  float* ldsP = (float*)(ldsB + C::B_ELEMS);        // LN partials [2][NW][MT]
+  float* ldsS = ldsP + 2 * NW * MT;                 // mu, rstd [2][MT]
 
   const int tid = threadIdx.x;
-  const int nthreads = 64 * NW;
-  const int wave = tid / SRX_WAVE;  // 0..NW-1 = within-piece tile position
   const int lane = tid % SRX_WAVE;
-  const long t0 = (long)blockIdx.x * 64;
+  const int wave = tid / SRX_WAVE;
+  const int mh = wave / NW, w = wave % NW;
+  const long t0 = (long)blockIdx.x * MT;
 
   srx_f32x16 acc[3][2];  // [piece][m-tile]
-#pragma unroll
-  for (int p = 0; p < 3; p++)
-#pragma unroll
-    for (int mi = 0; mi < 2; mi++)
-#pragma unroll
-      for (int rr = 0; rr < 16; rr++) acc[p][mi][rr] = 0.f;
+  mwe_tile_gemm<C>(X, Wt, is_start, is_end, T, t0, ldsA, ldsB, acc);
 
-  // ---- K loop: 3 sections x (W/16) MFMA K-steps
-  for (int s = 0; s < 3; s++) {
-    __syncthreads();
-    // stage A_s: A_s[r] = X[t0+r-1+s] (zeroed across doc bounds)
-    for (int r = tid; r < 64; r += nthreads) {
-      long t = t0 + r;
-      long src = t + s - 1;
-      bool zero = (s == 0 && (t == 0 || is_start[t])) ||
-                  (s == 2 && (t == T - 1 || is_end[t])) || src < 0 || src >= T;
-      bf16_t* dst = ldsA + r * WP;
-      const bf16_t* srcp = X + src * W;
-      for (int c = 0; c < W; c += 8) {
-        if (zero) {
-          *(srx_bf16x8*)(dst + c) = srx_bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        } else {
-          *(srx_bf16x8*)(dst + c) = *(const srx_bf16x8*)(srcp + c);
-        }
-      }
-    }
-    // stage B_s transposed: ldsB[j][k] = Wt[j][s*W + k]
-    for (int j = tid; j < 3 * W; j += nthreads) {
-      const bf16_t* srcp = Wt + (long)j * (3 * W) + s * W;
-      bf16_t* dst = ldsB + j * WP;
-      for (int c = 0; c < W; c += 8)
-        *(srx_bf16x8*)(dst + c) = *(const srx_bf16x8*)(srcp + c);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < W; k += 16) {
-      // A fragment (32x32x16 bf16): lane holds A[32*mi + (lane&31)]
-      // [k + 8*(lane>>5) + e], e=0..7 — one ds_read_b128
-      srx_bf16x8 afrag[2];
-#pragma unroll
-      for (int mi = 0; mi < 2; mi++) {
-        const bf16_t* ap =
-            ldsA + (32 * mi + (lane & 31)) * WP + k + 8 * (lane >> 5);
-        afrag[mi] = *(const srx_bf16x8*)ap;
-      }
-#pragma unroll
-      for (int p = 0; p < 3; p++) {
-        const int gcol = 32 * (p * NW + wave) + (lane & 31);
-        const bf16_t* bp = ldsB + gcol * WP + k + 8 * (lane >> 5);
-        srx_bf16x8 bfrag = *(const srx_bf16x8*)bp;
-#pragma unroll
-        for (int mi = 0; mi < 2; mi++) {
-          acc[p][mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              afrag[mi], bfrag, acc[p][mi], 0, 0, 0);
-        }
-      }
+  // ---- epilogue.  dropmask tile -> the free B region (16-byte loads)
+  if (dropmask) {
+    for (int id = tid; id < MT * (W / 8); id += NT) {
+      const int r = id / (W / 8), q = id % (W / 8);
+      if (t0 + r < T)
+        *(srx_u32x4_t*)(ldsM + r * WP + q * 8) =
+            *(const srx_u32x4_t*)(dropmask + (t0 + r) * W + q * 8);
     }
   }
 
-  // ---- epilogue: +bias, maxout over pieces, LN row stats, residual, store
-  const int wpcol = 32 * wave + (lane & 31);  // within-piece column
+  // +bias, maxout over pieces (fp32, first index wins ties)
+  const int col = 32 * w + (lane & 31);  // within-piece column
   float bias_p[3];
 #pragma unroll
-  for (int p = 0; p < 3; p++) bias_p[p] = bf2f(bias[p * W + wpcol]);
+  for (int p = 0; p < 3; p++) bias_p[p] = bf2f(bias[p * W + col]);
+  const float gv = bf2f(g[col]), bv = bf2f(b[col]);
 
   float mx[2][16];
   uint8_t arg[2][16];
-  float psum[2][16], psq[2][16];
 #pragma unroll
   for (int mi = 0; mi < 2; mi++) {
 #pragma unroll
@@ -146,53 +306,136 @@ __global__ __launch_bounds__(2 * W) void mwe_layer_fwd_kernel(
       }
       mx[mi][rr] = best;
       arg[mi][rr] = bp;
-      float s1 = best, s2 = best * best;
+    }
+  }
+
+  // LayerNorm row partials over this wave's 32 columns
+  const int b0 = lane & 1, b1 = (lane >> 1) & 1, b2 = (lane >> 2) & 1,
+            b3 = (lane >> 3) & 1;
+  const int rsel = 8 * b0 + 4 * b1 + 2 * b2 + b3;  // row index this lane ends with
 #pragma unroll
-      for (int off = 1; off < 32; off <<= 1) {
-        s1 += __shfl_xor(s1, off, SRX_WAVE);
-        s2 += __shfl_xor(s2, off, SRX_WAVE);
-      }
-      psum[mi][rr] = s1;  // row-partial over this wave's 32 columns
-      psq[mi][rr] = s2;
+  for (int mi = 0; mi < 2; mi++) {
+    float v1[16], v2[16];
+#pragma unroll
+    for (int rr = 0; rr < 16; rr++) {
+      v1[rr] = mx[mi][rr];
+      v2[rr] = mx[mi][rr] * mx[mi][rr];
+    }
+    const float s1 = mwe_row_sums(v1, lane);
+    const float s2 = mwe_row_sums(v2, lane);
+    if (((lane >> 4) & 1) == 0) {
+      const int r = 64 * mh + 32 * mi + (rsel & 3) + 8 * (rsel >> 2) + 4 * (lane >> 5);
+      ldsP[w * MT + r] = s1;
+      ldsP[(NW + w) * MT + r] = s2;
     }
   }
   __syncthreads();
-  if ((lane & 31) == 0) {  // lanes 0 and 32 (different row halves)
+  if (tid < MT) {
+    float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int mi = 0; mi < 2; mi++)
-#pragma unroll
-      for (int rr = 0; rr < 16; rr++) {
-        int r = 32 * mi + (rr & 3) + 8 * (rr >> 2) + 4 * (lane >> 5);
-        ldsP[wave * 64 + r] = psum[mi][rr];
-        ldsP[NW * 64 + wave * 64 + r] = psq[mi][rr];
-      }
+    for (int w2 = 0; w2 < NW; w2++) {
+      s1 += ldsP[w2 * MT + tid];
+      s2 += ldsP[(NW + w2) * MT + tid];
+    }
+    const float mu = s1 / W;
+    const float var = s2 / W - mu * mu;
+    const float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
+    ldsS[tid] = mu;
+    ldsS[MT + tid] = rstd;
+    if (t0 + tid < T) {
+      mu_out[t0 + tid] = mu;
+      rstd_out[t0 + tid] = rstd;
+    }
   }
   __syncthreads();
+
+  // normalise, mask, residual from the X image; results stay in LDS
 #pragma unroll
   for (int mi = 0; mi < 2; mi++) {
 #pragma unroll
     for (int rr = 0; rr < 16; rr++) {
-      int r = 32 * mi + (rr & 3) + 8 * (rr >> 2) + 4 * (lane >> 5);
-      float s1 = 0.f, s2 = 0.f;
-      for (int w2 = 0; w2 < NW; w2++) {
-        s1 += ldsP[w2 * 64 + r];
-        s2 += ldsP[NW * 64 + w2 * 64 + r];
-      }
-      float mu = s1 / W;
-      float var = s2 / W - mu * mu;
-      float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
-      long t = t0 + r;
-      if (wave == 0 && (lane & 31) == 0) {
-        mu_out[t] = mu;
-        rstd_out[t] = rstd;
-      }
-      float v = mx[mi][rr];
-      float y = (v - mu) * rstd * bf2f(g[wpcol]) + bf2f(b[wpcol]);
-      if (dropmask) y *= bf2f(dropmask[t * W + wpcol]);
-      y += bf2f(X[t * W + wpcol]);  // residual (L2-hot re-read)
-      Y[t * W + wpcol] = f2bf(y);
-      Mout[t * W + wpcol] = f2bf(v);
-      which[t * W + wpcol] = arg[mi][rr];
+      const int r = 64 * mh + 32 * mi + (rr & 3) + 8 * (rr >> 2) + 4 * (lane >> 5);
+      const float mu = ldsS[r], rstd = ldsS[MT + r];
+      const float v = mx[mi][rr];
+      float y = (v - mu) * rstd * gv + bv;
+      if (dropmask) y *= bf2f(ldsM[r * WP + col]);
+      y += bf2f(ldsA[(r + 1) * WP + col]);  // residual
+      ldsA[(r + 1) * WP + col] = f2bf(y);
+      ldsM[r * WP + col] = f2bf(v);
+      ldsWh[r * WHP + col] = arg[mi][rr];
+    }
+  }
+  __syncthreads();
+
+  // 16-byte row-contiguous stores
+  for (int id = tid; id < MT * (W / 8); id += NT) {
+    const int r = id / (W / 8), q = id % (W / 8);
+    if (t0 + r < T) {
+      *(srx_u32x4_t*)(Y + (t0 + r) * W + q * 8) =
+          *(const srx_u32x4_t*)(ldsA + (r + 1) * WP + q * 8);
+      *(srx_u32x4_t*)(Mout + (t0 + r) * W + q * 8) =
+          *(const srx_u32x4_t*)(ldsM + r * WP + q * 8);
+    }
+  }
+  for (int id = tid; id < MT * (W / 16); id += NT) {
+    const int r = id / (W / 16), q = id % (W / 16);
+    if (t0 + r < T)
+      *(srx_u32x4_t*)(which + (t0 + r) * W + q * 16) =
+          *(const srx_u32x4_t*)(ldsWh + r * WHP + q * 16);
+  }
+}
+
+// ---------------------------------------------------------- backward dX
+// dX = dY + seq2col_bwd(dPre @ weight) without materialising the [T, 3W]
+// product: fp32 accumulation over all three sections, one rounding.
+// WT is the launcher's transposed copy of the weight ([3W in, 3W out]),
+// so that section s's B rows n = WT[sW + n, :] are k-contiguous.
+template <int W>
+__global__ __launch_bounds__(4 * W) void mwe_bwd_dx_kernel(
+    const bf16_t* __restrict__ dPre,   // [T, 3W]
+    const bf16_t* __restrict__ WT,     // [3W, 3W] = weight^T, row-major
+    const uint8_t* __restrict__ is_start,
+    const uint8_t* __restrict__ is_end,
+    const bf16_t* __restrict__ dY,     // [T, W]
+    bf16_t* __restrict__ dX,           // [T, W]
+    long T) {
+  using C = MweCfg<W, true>;
+  constexpr int NW = C::NW, MT = C::MT, NT = C::NT;
+  constexpr int OP = W + 4;  // fp32 output tile row stride
+  static_assert(MT * OP * 4 <= C::A_ELEMS * 2, "output tile");
+  extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
+  bf16_t* ldsA = lds;
+  bf16_t* ldsB = lds + C::A_ELEMS;
+  float* ldsO = (float*)lds;  // epilogue: fp32 [MT][OP] over the A image
+
+  const int tid = threadIdx.x;
+  const int lane = tid % SRX_WAVE;
+  const int wave = tid / SRX_WAVE;
+  const int mh = wave / NW, w = wave % NW;
+  const long t0 = (long)blockIdx.x * MT;
+
+  srx_f32x16 acc[1][2];
+  mwe_tile_gemm<C>(dPre, WT, is_start, is_end, T, t0, ldsA, ldsB, acc);
+
+  const int col = 32 * w + (lane & 31);
+#pragma unroll
+  for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+    for (int rr = 0; rr < 16; rr++) {
+      const int r = 64 * mh + 32 * mi + (rr & 3) + 8 * (rr >> 2) + 4 * (lane >> 5);
+      ldsO[r * OP + col] = acc[0][mi][rr];
+    }
+  __syncthreads();
+  for (int id = tid; id < MT * (W / 8); id += NT) {
+    const int r = id / (W / 8), q = id % (W / 8);
+    if (t0 + r < T) {
+      float v[8], d[8];
+      ElemV<bf16_t, 8>::ld(dY + (t0 + r) * W + q * 8, d);
+      const float4 lo = *(const float4*)(ldsO + r * OP + q * 8);
+      const float4 hi = *(const float4*)(ldsO + r * OP + q * 8 + 4);
+      v[0] = lo.x + d[0]; v[1] = lo.y + d[1]; v[2] = lo.z + d[2]; v[3] = lo.w + d[3];
+      v[4] = hi.x + d[4]; v[5] = hi.y + d[5]; v[6] = hi.z + d[6]; v[7] = hi.w + d[7];
+      ElemV<bf16_t, 8>::st(dX + (t0 + r) * W + q * 8, v);
     }
   }
 }

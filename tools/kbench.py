@@ -52,6 +52,17 @@ def bench_mwe():
     dm = torch.ones(T, W, device=dev, dtype=torch.bfloat16)
     timeit("mwe_bwd_stage1 (T=1M,W=96)",
            lambda: hip.mwe_bwd_stage1(dY, dm, Mout, g, mu, rstd, which))
+    # dX: the composed path (GEMM + seq2col_bwd with the residual) against
+    # the fused kernel, on the same dPre
+    dPre = hip.mwe_bwd_stage1(dY, dm, Mout, g, mu, rstd, which)[0]
+    dX3 = dPre.mm(Wt)
+    timeit("dPre.mm(weight) (T=1M,W=96)", lambda: dPre.mm(Wt))
+    timeit("seq2col_bwd+res (T=1M,W=96)",
+           lambda: hip.seq2col_bwd(dX3, starts, ends, dY))
+    timeit("composed dX (T=1M,W=96)",
+           lambda: hip.seq2col_bwd(dPre.mm(Wt), starts, ends, dY))
+    timeit("mwe_bwd_dx (T=1M,W=96)",
+           lambda: hip.mwe_bwd_dx(dPre, Wt, starts, ends, dY))
 
 
 def bench_dpre():
