@@ -560,9 +560,9 @@ def parser_scatter_entries(entries, dPre32) -> None:
 class _MWELayer(torch.autograd.Function):
     """One MaxoutWindowEncoder block as a single hand-written MFMA kernel:
     Y = X + LN(maxout_3(seq2col(X) @ W^T + bias)).  Forward is the fused
-    gfx950 kernel (srx_mwe.hip.h); backward: fused stage 1 (mask x
-    layernorm_bwd x maxout scatter) -> dW GEMM (hipBLASLt) with seq2col
-    recomputed -> fused dX kernel (dPre @ W, seq2col_bwd and the residual)."""
+    gfx950 kernel (srx_mwe.hip.h); backward: one fused kernel for stage 1
+    (mask x layernorm_bwd x maxout scatter) and dX (dPre @ W, seq2col_bwd
+    and the residual) -> dW GEMM (hipBLASLt) with seq2col recomputed."""
 
     @staticmethod
     def forward(ctx, X, weight, bias, g, b, starts, ends, dropmask, eps):
@@ -583,15 +583,16 @@ class _MWELayer(torch.autograd.Function):
             dropmask = None
         hip = hip_ext()
         dY = dY.contiguous()
-        # stage 1 in ONE kernel: dropout mask x LN backward x maxout scatter
-        # + the dg/db/dbias column sums (was 3 kernels + 2 reduce passes)
-        dPre, dg32, db32, dbias32 = hip.mwe_bwd_stage1(
-            dY, dropmask, Mout, g, mu, rstd, which, deterministic())
+        # ONE kernel: stage 1 (dropout mask x LN backward x maxout scatter)
+        # per 128-row tile straight into the LDS image of the dX GEMM
+        # (dX = dY + seq2col_bwd(dPre @ weight)); dPre is written once for
+        # the dW GEMM and never read back.  The dg/db/dbias column sums are
+        # fixed-order (no atomics), so SRX_DETERMINISTIC needs no variant.
+        dPre, dX, dg32, db32, dbias32 = hip.mwe_bwd_fused(
+            dY, dropmask, Mout, g, mu, rstd, which, weight, starts, ends)
         # GEMM backwards (pre = X3 @ W^T)
         X3 = hip.seq2col_fwd(X, starts, ends)
         dW = mm_dw_chunked(dPre, X3)
-        # dX = dY + seq2col_bwd(dPre @ weight), fused (no [T,3W] product)
-        dX = hip.mwe_bwd_dx(dPre, weight, starts, ends, dY)
         return (dX, dW, dbias32.to(dY.dtype), dg32.to(dY.dtype),
                 db32.to(dY.dtype), None, None, None, None)
 

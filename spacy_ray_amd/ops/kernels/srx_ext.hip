@@ -1142,6 +1142,126 @@ at::Tensor mwe_bwd_dx(at::Tensor dPre, at::Tensor weight, at::Tensor starts,
   return dX;
 }
 
+// ------------------------------------- fused MWE backward (stage 1 + dX)
+template <int W>
+void launch_mwe_bwd_fused(const at::Tensor& dY,
+                          const c10::optional<at::Tensor>& dropmask,
+                          const at::Tensor& Mout, const at::Tensor& g,
+                          const at::Tensor& mu, const at::Tensor& rstd,
+                          const at::Tensor& which, const at::Tensor& WT,
+                          const at::Tensor& starts, const at::Tensor& ends,
+                          at::Tensor& dPre, at::Tensor& dX, at::Tensor& partials,
+                          long T, hipStream_t stream) {
+  using C = MweCfg<W, true>;
+  // the dX kernel's LDS: dPre halo image + double-buffered B chunks; the
+  // epilogue tiles and the column-sum partials reuse both regions
+  size_t lds_bytes = (size_t)(C::A_ELEMS + C::B_ELEMS) * sizeof(bf16_t);
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)mwe_bwd_fused_kernel<W>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_bytes);
+    attr_set = true;
+  }
+  dim3 grid((unsigned)((T + C::MT - 1) / C::MT));
+  hipLaunchKernelGGL((mwe_bwd_fused_kernel<W>), grid, dim3(C::NT), lds_bytes,
+                     stream, (const bf16_t*)dY.data_ptr(),
+                     dropmask ? (const bf16_t*)dropmask->data_ptr() : nullptr,
+                     (const bf16_t*)Mout.data_ptr(), (const bf16_t*)g.data_ptr(),
+                     mu.data_ptr<float>(), rstd.data_ptr<float>(),
+                     which.data_ptr<uint8_t>(), (const bf16_t*)WT.data_ptr(),
+                     starts.data_ptr<uint8_t>(), ends.data_ptr<uint8_t>(),
+                     (bf16_t*)dPre.data_ptr(), (bf16_t*)dX.data_ptr(),
+                     partials.data_ptr<float>(), T);
+}
+
+// mwe_bwd_stage1 + mwe_bwd_dx in one kernel: dPre is computed per 128-row
+// tile straight into the dX GEMM's LDS image and written to memory once
+// (for the dW GEMM), never read back.  The column sums leave as one fp32
+// row per tile and are added in a fixed order (no atomics): the same
+// kernel serves SRX_DETERMINISTIC.  Returns {dPre, dX, dg32, db32, dbias32}.
+std::vector<at::Tensor> mwe_bwd_fused(at::Tensor dY,
+                                      c10::optional<at::Tensor> dropmask,
+                                      at::Tensor Mout, at::Tensor g,
+                                      at::Tensor mu, at::Tensor rstd,
+                                      at::Tensor which, at::Tensor weight,
+                                      at::Tensor starts, at::Tensor ends) {
+  check_dev(dY);
+  check_dev(Mout);
+  check_dev(g);
+  check_dev(mu);
+  check_dev(rstd);
+  check_dev(which);
+  check_dev(starts);
+  check_dev(ends);
+  TORCH_CHECK(weight.is_cuda(), "expected a GPU tensor");
+  TORCH_CHECK(dY.scalar_type() == at::kBFloat16 &&
+                  Mout.scalar_type() == at::kBFloat16 &&
+                  g.scalar_type() == at::kBFloat16 &&
+                  weight.scalar_type() == at::kBFloat16,
+              "mwe_bwd_fused is bf16-only");
+  TORCH_CHECK(dY.dim() == 2 && weight.dim() == 2,
+              "mwe_bwd_fused expects 2-d tensors");
+  long T = dY.size(0);
+  int W = (int)dY.size(1);
+  TORCH_CHECK(W == 96 || W == 128, "mwe_bwd_fused supports W in {96,128}");
+  TORCH_CHECK(T % 64 == 0, "mwe_bwd_fused needs T % 64 == 0 (TokenBatch pads)");
+  TORCH_CHECK(weight.size(0) == 3 * W && weight.size(1) == 3 * W,
+              "weight must be [3W,3W]");
+  TORCH_CHECK(starts.numel() == T && ends.numel() == T,
+              "starts/ends must have T entries");
+  TORCH_CHECK(starts.scalar_type() == at::kByte && ends.scalar_type() == at::kByte,
+              "starts/ends must be uint8");
+  TORCH_CHECK(Mout.dim() == 2 && Mout.size(0) == T && Mout.size(1) == W,
+              "Mout must be [T,W]");
+  TORCH_CHECK(which.scalar_type() == at::kByte && which.dim() == 2 &&
+                  which.size(0) == T && which.size(1) == W,
+              "which must be uint8 [T,W]");
+  TORCH_CHECK(mu.scalar_type() == at::kFloat && rstd.scalar_type() == at::kFloat &&
+                  mu.numel() == T && rstd.numel() == T,
+              "mu/rstd must be fp32 with T entries");
+  TORCH_CHECK(g.numel() == W, "g must have W entries");
+  if (dropmask) {
+    check_dev(*dropmask);
+    TORCH_CHECK(dropmask->scalar_type() == at::kBFloat16 && dropmask->dim() == 2 &&
+                    dropmask->size(0) == T && dropmask->size(1) == W,
+                "dropmask must be bf16 [T,W]");
+  }
+  auto dPre = at::empty({T, 3L * W}, dY.options());
+  auto dX = at::empty_like(dY);
+  auto f32 = dY.options().dtype(at::kFloat);
+  if (T == 0) {
+    return {dPre, dX, at::zeros({W}, f32), at::zeros({W}, f32),
+            at::zeros({3L * W}, f32)};
+  }
+  // k-contiguous B rows: section s, output column n -> WT[sW + n, :]
+  auto WT = weight.t().contiguous();
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const int ncols = 5 * W;
+  long n = (T + 127) / 128;
+  auto part = at::empty({n, (long)ncols}, f32);
+  if (W == 96)
+    launch_mwe_bwd_fused<96>(dY, dropmask, Mout, g, mu, rstd, which, WT, starts,
+                             ends, dPre, dX, part, T, stream);
+  else
+    launch_mwe_bwd_fused<128>(dY, dropmask, Mout, g, mu, rstd, which, WT, starts,
+                              ends, dPre, dX, part, T, stream);
+  // per-tile rows -> one row, 64 rows per block per level, in row order
+  const int R = 64;
+  do {
+    long nb = (n + R - 1) / R;
+    auto out = at::empty({nb, (long)ncols}, f32);
+    hipLaunchKernelGGL(mwe_colsum_kernel, dim3((unsigned)nb, (ncols + 63) / 64),
+                       dim3(64), 0, stream, part.data_ptr<float>(),
+                       out.data_ptr<float>(), n, R, ncols);
+    part = out;
+    n = nb;
+  } while (n > 1);
+  auto sums = part.view({(long)ncols});
+  return {dPre, dX, sums.narrow(0, 0, W), sums.narrow(0, W, W),
+          sums.narrow(0, 2L * W, 3L * W)};
+}
+
 // --------------------------------------------- fused transition step (C++)
 // One python call per transition step: state scorer kernel + upper GEMM +
 // on-device action selection, with a C++ autograd node so the per-step
@@ -1283,6 +1403,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mwe_layer_fwd", &mwe_layer_fwd);
   m.def("mwe_bwd_dx", &mwe_bwd_dx, py::arg("dPre"), py::arg("weight"),
         py::arg("starts"), py::arg("ends"), py::arg("dY"));
+  m.def("mwe_bwd_fused", &mwe_bwd_fused, py::arg("dY"), py::arg("dropmask"),
+        py::arg("Mout"), py::arg("g"), py::arg("mu"), py::arg("rstd"),
+        py::arg("which"), py::arg("weight"), py::arg("starts"), py::arg("ends"));
   m.def("fused_step", &fusedstep::fused_step);
   m.def("fused_entries_take", &fusedstep::fused_entries_take);
   m.def("transition_ce", &transition_ce, py::arg("scores"), py::arg("gold"),

@@ -36,17 +36,27 @@
 // staged X image; Y overwrites the X image, Mout the mask tile, `which`
 // its own tile, and all three leave with 16-byte row-contiguous stores.
 //
+// The training backward is mwe_bwd_fused_kernel: stage 1 (dropmask x
+// LayerNorm backward x maxout scatter) computed per tile straight into the
+// dX GEMM's A image, so the [T, 3W] dPre is written once (for the dW GEMM)
+// and never read back; column sums without atomics.  See its own comment.
+// mwe_bwd_stage1_kernel and mwe_bwd_dx_kernel stay as the two-kernel form
+// (tests, tools/kbench.py).
+//
 // Compiler resource report (hipcc -Rpass-analysis=kernel-resource-usage,
-// gfx950; AGPR 0 and scratch 0 in all four):
+// gfx950; AGPR 0 and scratch 0 in all six):
 //   mwe_layer_fwd_kernel<96>   147 VGPR  LDS  77,216 B  2 workgroups (12 waves) / CU
 //   mwe_layer_fwd_kernel<128>  149 VGPR  LDS 101,920 B  1 workgroup  ( 8 waves) / CU
-//   mwe_bwd_dx_kernel<96>      113 VGPR  LDS 116,896 B  1 workgroup  ( 6 waves) / CU
+//   mwe_bwd_dx_kernel<96>      112 VGPR  LDS 116,896 B  1 workgroup  ( 6 waves) / CU
 //   mwe_bwd_dx_kernel<128>     126 VGPR  LDS 155,168 B  1 workgroup  ( 8 waves) / CU
+//   mwe_bwd_fused_kernel<96>   185 VGPR  LDS 116,896 B  1 workgroup  ( 6 waves) / CU
+//   mwe_bwd_fused_kernel<128>  163 VGPR  LDS 155,168 B  1 workgroup  ( 8 waves) / CU
 // Measured at T=1M, W=96 (MI355X): forward 1.32 -> 0.54 ms, dX 0.77
-// (GEMM + seq2col_bwd) -> 0.47 ms; see profiles/README.md.
+// (GEMM + seq2col_bwd) -> 0.47 ms, stage 1 + dX 1.02 + 0.48 -> 0.80 ms
+// fused; see profiles/README.md.
 //
 // Saved for the backward: maxout output M, argmax, mu, rstd (backward =
-// mwe_bwd_stage1 + recomputed seq2col + dW GEMM + mwe_bwd_dx).
+// mwe_bwd_fused + recomputed seq2col + dW GEMM).
 #pragma once
 #include "srx_common.hip.h"
 
@@ -105,7 +115,9 @@ __device__ __forceinline__ void mwe_b_store(bf16_t* ldsBbuf, int tid,
   }
 }
 
-// acc[p][mi] (+)= sum over the 3 sections of mask_s(row) * A[row + shift_s]
+// The tile GEMM, in four separable steps (mwe_tile_gemm below runs them in
+// order; mwe_bwd_fused_kernel builds the A image itself):
+//   acc[p][mi] = sum over the 3 sections of mask_s(row) * A[row + shift_s]
 // times B_s, for this wave's rows [64 mh + 32 mi, +32) and B rows
 // 32 (p NW + w) + [0, 32).  A is [T, KA]; image row i holds A[t0 - 1 + i]
 // (zero outside [0, T)).  Section s of the forward multiplies A[t - 1 + s]
@@ -113,50 +125,34 @@ __device__ __forceinline__ void mwe_b_store(bf16_t* ldsBbuf, int tid,
 // at a doc end / t=T-1; section s of the backward multiplies A[t + 1 - s]
 // by Bm[sW + n, k] and is dropped for s=0 when t+1 starts a doc / is T and
 // for s=2 when t-1 ends a doc / t=0 (the masks of seq2col_bwd_kernel).
-// Ends with a barrier: both LDS regions are free afterwards.
+
+// A halo image from global memory: all loads first, then all LDS writes
 template <class C>
-__device__ __forceinline__ void mwe_tile_gemm(
-    const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm,
-    const uint8_t* __restrict__ is_start, const uint8_t* __restrict__ is_end,
-    long T, long t0, bf16_t* ldsA, bf16_t* ldsB,
-    srx_f32x16 (&acc)[C::NP][2]) {
-  const int tid = threadIdx.x;
-  const int lane = tid % SRX_WAVE;
-  const int wave = tid / SRX_WAVE;
-  const int mh = wave / C::NW, w = wave % C::NW;
-
+__device__ __forceinline__ void mwe_stage_a(const bf16_t* __restrict__ A, long T,
+                                            long t0, int tid, bf16_t* ldsA) {
+  srx_u32x4_t v[C::A_ITERS];
 #pragma unroll
-  for (int p = 0; p < C::NP; p++)
-#pragma unroll
-    for (int mi = 0; mi < 2; mi++)
-#pragma unroll
-      for (int rr = 0; rr < 16; rr++) acc[p][mi][rr] = 0.f;
-
-  srx_u32x4_t pf[C::PF];
-  mwe_b_fetch<C>(Bm, 0, tid, pf);
-
-  // A halo image: all loads first, then all LDS writes
-  {
-    srx_u32x4_t v[C::A_ITERS];
-#pragma unroll
-    for (int it = 0; it < C::A_ITERS; it++) {
-      const int id = it * C::NT + tid;
-      const int i = id / (C::KA / 8), q = id % (C::KA / 8);
-      const long t = t0 - 1 + i;
-      v[it] = srx_u32x4_t{0u, 0u, 0u, 0u};
-      if (i < C::A_ROWS && t >= 0 && t < T)
-        v[it] = *(const srx_u32x4_t*)(A + t * C::KA + q * 8);
-    }
-#pragma unroll
-    for (int it = 0; it < C::A_ITERS; it++) {
-      const int id = it * C::NT + tid;
-      const int i = id / (C::KA / 8), q = id % (C::KA / 8);
-      if (i < C::A_ROWS) *(srx_u32x4_t*)(ldsA + i * C::AP + q * 8) = v[it];
-    }
+  for (int it = 0; it < C::A_ITERS; it++) {
+    const int id = it * C::NT + tid;
+    const int i = id / (C::KA / 8), q = id % (C::KA / 8);
+    const long t = t0 - 1 + i;
+    v[it] = srx_u32x4_t{0u, 0u, 0u, 0u};
+    if (i < C::A_ROWS && t >= 0 && t < T)
+      v[it] = *(const srx_u32x4_t*)(A + t * C::KA + q * 8);
   }
+#pragma unroll
+  for (int it = 0; it < C::A_ITERS; it++) {
+    const int id = it * C::NT + tid;
+    const int i = id / (C::KA / 8), q = id % (C::KA / 8);
+    if (i < C::A_ROWS) *(srx_u32x4_t*)(ldsA + i * C::AP + q * 8) = v[it];
+  }
+}
 
-  // per-lane section masks of its two A rows: bit s set = section s is zero
-  int zmask[2];
+// per-lane section masks of its two A rows: bit s set = section s is zero
+template <class C>
+__device__ __forceinline__ void mwe_section_masks(
+    const uint8_t* __restrict__ is_start, const uint8_t* __restrict__ is_end,
+    long T, long t0, int mh, int lane, int (&zmask)[2]) {
 #pragma unroll
   for (int mi = 0; mi < 2; mi++) {
     const long t = t0 + 64 * mh + 32 * mi + (lane & 31);
@@ -174,9 +170,27 @@ __device__ __forceinline__ void mwe_tile_gemm(
     }
     zmask[mi] = z;
   }
+}
 
-  mwe_b_store<C>(ldsB, tid, pf);
-  __syncthreads();
+// The K-chunk loop.  On entry the A image and B chunk 0 (buffer 0) are in
+// LDS and a barrier has been passed; `pf` is scratch for the B prefetch.
+// Ends with a barrier: both LDS regions are free afterwards.
+template <class C>
+__device__ __forceinline__ void mwe_chunk_loop(
+    const bf16_t* __restrict__ Bm, const bf16_t* ldsA, bf16_t* ldsB,
+    const int (&zmask)[2], srx_u32x4_t (&pf)[C::PF],
+    srx_f32x16 (&acc)[C::NP][2]) {
+  const int tid = threadIdx.x;
+  const int lane = tid % SRX_WAVE;
+  const int wave = tid / SRX_WAVE;
+  const int mh = wave / C::NW, w = wave % C::NW;
+
+#pragma unroll
+  for (int p = 0; p < C::NP; p++)
+#pragma unroll
+    for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+      for (int rr = 0; rr < 16; rr++) acc[p][mi][rr] = 0.f;
 
   for (int c = 0; c < C::NC; c++) {
     if (c + 1 < C::NC) mwe_b_fetch<C>(Bm, c + 1, tid, pf);
@@ -210,6 +224,27 @@ __device__ __forceinline__ void mwe_tile_gemm(
       mwe_b_store<C>(ldsB + ((c + 1) & 1) * (C::NBR * C::BP), tid, pf);
     __syncthreads();
   }
+}
+
+// A from global memory: B chunk 0 prefetch, A image, masks, chunk loop.
+template <class C>
+__device__ __forceinline__ void mwe_tile_gemm(
+    const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm,
+    const uint8_t* __restrict__ is_start, const uint8_t* __restrict__ is_end,
+    long T, long t0, bf16_t* ldsA, bf16_t* ldsB,
+    srx_f32x16 (&acc)[C::NP][2]) {
+  const int tid = threadIdx.x;
+  const int lane = tid % SRX_WAVE;
+  const int mh = (tid / SRX_WAVE) / C::NW;
+
+  srx_u32x4_t pf[C::PF];
+  mwe_b_fetch<C>(Bm, 0, tid, pf);
+  mwe_stage_a<C>(A, T, t0, tid, ldsA);
+  int zmask[2];
+  mwe_section_masks<C>(is_start, is_end, T, t0, mh, lane, zmask);
+  mwe_b_store<C>(ldsB, tid, pf);
+  __syncthreads();
+  mwe_chunk_loop<C>(Bm, ldsA, ldsB, zmask, pf, acc);
 }
 
 // One halving step of the row-sum butterfly: the lane keeps the half of
@@ -508,4 +543,242 @@ __global__ void mwe_bwd_stage1_kernel(
       if (dbias_loc[c * 3 + q] != 0.f)
         srx_atomic_add<DET>(dbias32, (long)q * W + w, dbias_loc[c * 3 + q]);
   }
+}
+
+// ------------------------------- fused MWE backward: stage 1 + dX, one pass
+// mwe_bwd_stage1_kernel and mwe_bwd_dx_kernel in one launch: the stage-1
+// result of a 128-row tile (plus its two halo rows, recomputed per tile) is
+// written straight into the dX GEMM's LDS A image instead of making the
+// round trip through the [T, 3W] dPre tensor in HBM.  dPre still leaves
+// once (the dW GEMM reads it), with 16-byte row-contiguous stores from the
+// image.
+//
+// Prologue mapping: 16 lanes per row, 8 columns per lane (lanes 12..15 idle
+// at W = 96), NT / 16 rows per pass; every global load is 16 bytes (`which`:
+// 8) and all passes' loads are issued before the first is used.  The LN row
+// sums are four xor-shuffles.  The fp32 arithmetic is that of
+// mwe_bwd_stage1_kernel; only the order of the row sums differs.
+//
+// Column sums: a thread owns the same 8 columns in every pass, so dg / db /
+// dbias accumulate in 40 registers over the tile's own rows < T (never the
+// halo), are folded over the wave's four row groups by shuffles, over the
+// waves through the free B region, and leave as one fp32 row [5W] =
+// dg | db | dbias per workgroup.  mwe_colsum_kernel adds those rows in a
+// fixed order: no atomics, bit-reproducible in every mode.
+template <int W>
+__global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
+    const bf16_t* __restrict__ dY,        // [T, W]
+    const bf16_t* __restrict__ dropmask,  // [T, W] or nullptr
+    const bf16_t* __restrict__ Mout,      // [T, W]
+    const bf16_t* __restrict__ g,         // [W]
+    const float* __restrict__ mu,         // [T]
+    const float* __restrict__ rstd,       // [T]
+    const uint8_t* __restrict__ which,    // [T, W]
+    const bf16_t* __restrict__ WT,        // [3W, 3W] = weight^T, row-major
+    const uint8_t* __restrict__ is_start,
+    const uint8_t* __restrict__ is_end,
+    bf16_t* __restrict__ dPre,            // [T, 3W]
+    bf16_t* __restrict__ dX,              // [T, W]
+    float* __restrict__ partials,         // [gridDim.x, 5W]
+    long T) {
+  using C = MweCfg<W, true>;
+  constexpr int NW = C::NW, MT = C::MT, NT = C::NT, AP = C::AP;
+  constexpr int Q = W / 8;                        // 16-byte groups per row
+  constexpr int RG = NT / 16;                     // rows per prologue pass
+  constexpr int NPASS = (C::A_ROWS + RG - 1) / RG;
+  constexpr int NWAVE = NT / SRX_WAVE;
+  constexpr int OP = W + 4;  // fp32 output tile row stride
+  static_assert(MT * OP * 4 <= C::A_ELEMS * 2, "output tile");
+  static_assert(NWAVE * 5 * W * 4 <= C::B_ELEMS * 2, "column-sum partials");
+  extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
+  bf16_t* ldsA = lds;
+  bf16_t* ldsB = lds + C::A_ELEMS;
+  float* ldsO = (float*)lds;   // epilogue: fp32 [MT][OP] over the A image
+  float* ldsC = (float*)ldsB;  // epilogue: column sums [NWAVE][5W] over B
+
+  const int tid = threadIdx.x;
+  const int lane = tid % SRX_WAVE;
+  const int wave = tid / SRX_WAVE;
+  const int mh = wave / NW, w = wave % NW;
+  const long t0 = (long)blockIdx.x * MT;
+
+  srx_u32x4_t pf[C::PF];
+  mwe_b_fetch<C>(WT, 0, tid, pf);
+
+  // ---- stage-1 prologue
+  const int q = tid & 15, rg = tid >> 4;
+  const bool qv = q < Q;
+  float gv[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) gv[j] = 0.f;
+  if (qv) ElemV<bf16_t, 8>::ld(g + q * 8, gv);
+
+  srx_u32x4_t rdy[NPASS], rmk[NPASS], rmo[NPASS];
+  uint2 rwh[NPASS];
+  float rmu[NPASS], rrs[NPASS];
+#pragma unroll
+  for (int ps = 0; ps < NPASS; ps++) {
+    const int i = ps * RG + rg;
+    const long t = t0 - 1 + i;
+    rdy[ps] = srx_u32x4_t{0u, 0u, 0u, 0u};
+    rmk[ps] = srx_u32x4_t{0u, 0u, 0u, 0u};
+    rmo[ps] = srx_u32x4_t{0u, 0u, 0u, 0u};
+    rwh[ps] = make_uint2(0u, 0u);
+    rmu[ps] = 0.f;
+    rrs[ps] = 0.f;
+    if (qv && i < C::A_ROWS && t >= 0 && t < T) {
+      rdy[ps] = *(const srx_u32x4_t*)(dY + t * W + q * 8);
+      if (dropmask) rmk[ps] = *(const srx_u32x4_t*)(dropmask + t * W + q * 8);
+      rmo[ps] = *(const srx_u32x4_t*)(Mout + t * W + q * 8);
+      rwh[ps] = *(const uint2*)(which + t * W + q * 8);
+      rmu[ps] = mu[t];
+      rrs[ps] = rstd[t];
+    }
+  }
+
+  float dg_loc[8], db_loc[8], dbias_loc[3][8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    dg_loc[j] = 0.f;
+    db_loc[j] = 0.f;
+    dbias_loc[0][j] = dbias_loc[1][j] = dbias_loc[2][j] = 0.f;
+  }
+
+#pragma unroll
+  for (int ps = 0; ps < NPASS; ps++) {
+    const int i = ps * RG + rg;
+    const long t = t0 - 1 + i;
+    const bool live = qv && i < C::A_ROWS && t >= 0 && t < T;
+    const bool own = live && i >= 1 && i <= MT;
+    const float m = rmu[ps], r = rrs[ps];
+    float d[8], xh[8], dxh[8];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const int sh = 16 * (j & 1);
+      d[j] = bf2f((bf16_t)((rdy[ps][j >> 1] >> sh) & 0xffffu));
+      if (dropmask) d[j] *= bf2f((bf16_t)((rmk[ps][j >> 1] >> sh) & 0xffffu));
+      xh[j] = (bf2f((bf16_t)((rmo[ps][j >> 1] >> sh) & 0xffffu)) - m) * r;
+      dxh[j] = d[j] * gv[j];
+      s1 += dxh[j];
+      s2 += dxh[j] * xh[j];
+    }
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+      s1 += __shfl_xor(s1, off, SRX_WAVE);
+      s2 += __shfl_xor(s2, off, SRX_WAVE);
+    }
+    s1 = s1 / W;
+    s2 = s2 / W;
+    uint32_t hb[8], wh[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const float dM = r * (dxh[j] - s1 - xh[j] * s2);
+      wh[j] = ((j < 4 ? rwh[ps].x : rwh[ps].y) >> (8 * (j & 3))) & 0xffu;
+      hb[j] = live ? (uint32_t)f2bf(dM) : 0u;
+      if (own) {
+        dg_loc[j] += d[j] * xh[j];
+        db_loc[j] += d[j];
+#pragma unroll
+        for (int p = 0; p < 3; p++) dbias_loc[p][j] += (wh[j] == (uint32_t)p) ? dM : 0.f;
+      }
+    }
+    // expanded row: dM at piece `which`, exact zero in the other two
+    if (qv && i < C::A_ROWS) {
+#pragma unroll
+      for (int p = 0; p < 3; p++) {
+        srx_u32x4_t o;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          o[k] = (wh[2 * k] == (uint32_t)p ? hb[2 * k] : 0u) |
+                 ((wh[2 * k + 1] == (uint32_t)p ? hb[2 * k + 1] : 0u) << 16);
+        *(srx_u32x4_t*)(ldsA + i * AP + p * W + q * 8) = o;
+      }
+    }
+  }
+
+  int zmask[2];
+  mwe_section_masks<C>(is_start, is_end, T, t0, mh, lane, zmask);
+  mwe_b_store<C>(ldsB, tid, pf);
+  __syncthreads();
+
+  // ---- dPre out: the tile's own rows, before the epilogue reuses the image
+  for (int id = tid; id < MT * (3 * Q); id += NT) {
+    const int r = id / (3 * Q), c = id % (3 * Q);
+    if (t0 + r < T)
+      *(srx_u32x4_t*)(dPre + (t0 + r) * (3 * W) + c * 8) =
+          *(const srx_u32x4_t*)(ldsA + (r + 1) * AP + c * 8);
+  }
+
+  srx_f32x16 acc[1][2];
+  mwe_chunk_loop<C>(WT, ldsA, ldsB, zmask, pf, acc);
+
+  // ---- column sums: fold the wave's 4 row groups, park per wave in LDS
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+#pragma unroll
+    for (int off = 16; off < SRX_WAVE; off <<= 1) {
+      dg_loc[j] += __shfl_xor(dg_loc[j], off, SRX_WAVE);
+      db_loc[j] += __shfl_xor(db_loc[j], off, SRX_WAVE);
+#pragma unroll
+      for (int p = 0; p < 3; p++)
+        dbias_loc[p][j] += __shfl_xor(dbias_loc[p][j], off, SRX_WAVE);
+    }
+  }
+  if (lane < 16 && qv) {
+    float* row = ldsC + wave * (5 * W) + q * 8;
+    ElemV<float, 4>::st(row, dg_loc);
+    ElemV<float, 4>::st(row + 4, dg_loc + 4);
+    ElemV<float, 4>::st(row + W, db_loc);
+    ElemV<float, 4>::st(row + W + 4, db_loc + 4);
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+      ElemV<float, 4>::st(row + (2 + p) * W, dbias_loc[p]);
+      ElemV<float, 4>::st(row + (2 + p) * W + 4, dbias_loc[p] + 4);
+    }
+  }
+
+  // ---- dX epilogue (as mwe_bwd_dx_kernel)
+  const int col = 32 * w + (lane & 31);
+#pragma unroll
+  for (int mi = 0; mi < 2; mi++)
+#pragma unroll
+    for (int rr = 0; rr < 16; rr++) {
+      const int r = 64 * mh + 32 * mi + (rr & 3) + 8 * (rr >> 2) + 4 * (lane >> 5);
+      ldsO[r * OP + col] = acc[0][mi][rr];
+    }
+  __syncthreads();
+  for (int id = tid; id < MT * Q; id += NT) {
+    const int r = id / Q, qq = id % Q;
+    if (t0 + r < T) {
+      float v[8], d[8];
+      ElemV<bf16_t, 8>::ld(dY + (t0 + r) * W + qq * 8, d);
+      const float4 lo = *(const float4*)(ldsO + r * OP + qq * 8);
+      const float4 hi = *(const float4*)(ldsO + r * OP + qq * 8 + 4);
+      v[0] = lo.x + d[0]; v[1] = lo.y + d[1]; v[2] = lo.z + d[2]; v[3] = lo.w + d[3];
+      v[4] = hi.x + d[4]; v[5] = hi.y + d[5]; v[6] = hi.z + d[6]; v[7] = hi.w + d[7];
+      ElemV<bf16_t, 8>::st(dX + (t0 + r) * W + qq * 8, v);
+    }
+  }
+  for (int c = tid; c < 5 * W; c += NT) {
+    float s = 0.f;
+#pragma unroll
+    for (int wv = 0; wv < NWAVE; wv++) s += ldsC[wv * (5 * W) + c];
+    partials[(long)blockIdx.x * (5 * W) + c] = s;
+  }
+}
+
+// out[b, c] = sum over rows [b R, min((b+1) R, n)) of in[:, c], added in row
+// order in fp64 and rounded to fp32 once: the fixed-order reduction of the
+// per-tile column sums above (applied until one row is left).
+__global__ void mwe_colsum_kernel(const float* __restrict__ in,
+                                  float* __restrict__ out, long n, int R,
+                                  int ncols) {
+  const int c = blockIdx.y * blockDim.x + threadIdx.x;
+  if (c >= ncols) return;
+  const long r0 = (long)blockIdx.x * R;
+  const long r1 = r0 + R < n ? r0 + R : n;
+  double s = 0.0;
+  for (long r = r0; r < r1; r++) s += (double)in[r * ncols + c];
+  out[(long)blockIdx.x * ncols + c] = (float)s;
 }

@@ -63,6 +63,11 @@ def bench_mwe():
            lambda: hip.seq2col_bwd(dPre.mm(Wt), starts, ends, dY))
     timeit("mwe_bwd_dx (T=1M,W=96)",
            lambda: hip.mwe_bwd_dx(dPre, Wt, starts, ends, dY))
+    # stage 1 + dX in one kernel: compare with the sum of the
+    # mwe_bwd_stage1 and mwe_bwd_dx lines above
+    timeit("mwe_bwd_fused (T=1M,W=96)",
+           lambda: hip.mwe_bwd_fused(dY, dm, Mout, g, mu, rstd, which, Wt,
+                                     starts, ends))
 
 
 def bench_dpre():
