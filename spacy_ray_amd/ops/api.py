@@ -503,6 +503,32 @@ class _TransitionLoopLoss(torch.autograd.Function):
                 None)
 
 
+class _TransitionLoopLossFused(_TransitionLoopLoss):
+    """_TransitionLoopLoss whose CE already ran inside the GPU state machine
+    (gpu_arceager / gpu_biluo with fuse_ce=True): forward takes the
+    precomputed (dScores, colsum, loss_count) in the slots that held
+    (scores, gold, valid) and launches nothing; the backward is the
+    inherited one."""
+
+    @staticmethod
+    def forward(ctx, pre, lower_b, upperW, upperB, dScores, colsum,
+                loss_count, feats, which, hidden, doc_off, doc_lens, cap_mult,
+                maxlen, doc_total):
+        ctx.save_for_backward(dScores, colsum, feats, which, hidden, upperW)
+        ctx.pre_shape = tuple(pre.shape)
+        ctx.pre_dtype = pre.dtype
+        ctx.doc_layout = (doc_off, doc_lens, cap_mult, maxlen, doc_total)
+        return loss_count[0]
+
+
+def fused_ce_enabled(n_actions: int) -> bool:
+    """Whether the GPU state machines compute the transition CE in-kernel.
+    Off in deterministic mode (transition_ce keeps its int64 fixed-point
+    colsum), past the fused path's A <= 256, and with SRX_FUSED_CE=0."""
+    return (os.environ.get("SRX_FUSED_CE", "1") == "1"
+            and not deterministic() and n_actions <= 256)
+
+
 def transition_loop_loss(pre, lower_b, upperW, upperB, scores, gold, valid,
                          feats, which, hidden, doc_off=None, doc_lens=None,
                          cap_mult=1, maxlen=0, doc_total=0):
@@ -510,6 +536,16 @@ def transition_loop_loss(pre, lower_b, upperW, upperB, scores, gold, valid,
                                      gold, valid, feats, which, hidden,
                                      doc_off, doc_lens, cap_mult, maxlen,
                                      doc_total)
+
+
+def transition_loop_loss_fused(pre, lower_b, upperW, upperB, dScores, colsum,
+                               loss_count, feats, which, hidden, doc_off=None,
+                               doc_lens=None, cap_mult=1, maxlen=0,
+                               doc_total=0):
+    return _TransitionLoopLossFused.apply(pre, lower_b, upperW, upperB,
+                                          dScores, colsum, loss_count, feats,
+                                          which, hidden, doc_off, doc_lens,
+                                          cap_mult, maxlen, doc_total)
 
 
 class _InjectGrad(torch.autograd.Function):

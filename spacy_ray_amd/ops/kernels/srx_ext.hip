@@ -1361,11 +1361,11 @@ std::vector<at::Tensor> srx_gpu_arceager(
     at::Tensor pre, at::Tensor off, at::Tensor lens, at::Tensor gh,
     at::Tensor gl, at::Tensor kids_off, at::Tensor kids, at::Tensor lowerB,
     at::Tensor upperW, at::Tensor upperB, int64_t total, int64_t n_labels,
-    bool train);
+    bool train, bool fuse_ce);
 std::vector<at::Tensor> srx_gpu_biluo(
     at::Tensor pre, at::Tensor off, at::Tensor lens, at::Tensor gold,
     at::Tensor lowerB, at::Tensor upperW, at::Tensor upperB, int64_t total,
-    int64_t n_types, bool train);
+    int64_t n_types, bool train, bool fuse_ce);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("seq2col_fwd", &seq2col_fwd);
@@ -1419,10 +1419,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lens"), py::arg("gh"), py::arg("gl"), py::arg("kids_off"),
         py::arg("kids"), py::arg("lowerB"), py::arg("upperW"),
         py::arg("upperB"), py::arg("total"), py::arg("n_labels"),
-        py::arg("train"));
+        py::arg("train"), py::arg("fuse_ce") = false);
   m.def("gpu_biluo", &srx_gpu_biluo, py::arg("pre"), py::arg("off"),
         py::arg("lens"), py::arg("gold"), py::arg("lowerB"), py::arg("upperW"),
         py::arg("upperB"), py::arg("total"), py::arg("n_types"),
-        py::arg("train"));
+        py::arg("train"), py::arg("fuse_ce") = false);
   m.attr("GPU_STATE_MAXLEN") = 128;
 }

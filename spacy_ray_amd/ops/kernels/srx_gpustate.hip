@@ -85,9 +85,122 @@ __device__ __forceinline__ float gs_rowdot64<float>(const float* wrow,
   return acc;
 }
 
+// ------------------------------------------------------ fused transition CE
+// CE=true (training only) moves transition_ce_kernel's row arithmetic
+// (srx_softmax_reduce.hip.h) into the step: the wave already holds the
+// row's scores and its valid / gold flags, so it writes dScores into the
+// slot that held the scores and never materialises the two mask arenas.
+// The CE runs on the T-ROUNDED score — what transition_ce reads back from
+// the arena — with the same per-lane chunk order and wave_reduce_sum, so
+// dScores is what the two-kernel path produces.  Loss, supervised-row
+// count and the dScores column sums accumulate in per-lane registers over
+// every step of every doc a wave runs and leave as ONE fp32 row per wave
+// ([n_waves, A + 2]); gs_colsum_kernel folds the rows in a fixed order.
+constexpr int GS_CE_CHUNKS = 4;  // A <= 256: transition_ce's own limit
+
+template <typename T>
+__device__ __forceinline__ float gs_round(float v);
+template <>
+__device__ __forceinline__ float gs_round<bf16_t>(float v) {
+  return bf2f(f2bf(v));
+}
+template <>
+__device__ __forceinline__ float gs_round<float>(float v) { return v; }
+
+struct GsCeAcc {
+  float col[GS_CE_CHUNKS];  // sum over rows of dScores[:, lane + 64 c]
+  float loss, count;
+};
+
+__device__ __forceinline__ void gs_ce_init(GsCeAcc& s) {
+#pragma unroll
+  for (int c = 0; c < GS_CE_CHUNKS; c++) s.col[c] = 0.f;
+  s.loss = 0.f;
+  s.count = 0.f;
+}
+
+// One row: x = rounded scores; flags bit 2c = column lane + 64c is valid,
+// bit 2c + 1 = it is gold (both clear past A); cnt = number of gold columns
+// (wave-uniform).  cnt == 0 is a row without supervision: nothing is
+// stored (the arena is pre-zeroed) or counted.
+template <typename T>
+__device__ __forceinline__ void gs_ce_row(const float (&x)[GS_CE_CHUNKS],
+                                          unsigned flags, int cnt,
+                                          T* __restrict__ drow, int lane,
+                                          int A, GsCeAcc& s) {
+  if (cnt == 0) return;
+  bool vv[GS_CE_CHUNKS], gg[GS_CE_CHUNKS];
+#pragma unroll
+  for (int c = 0; c < GS_CE_CHUNKS; c++) {
+    vv[c] = (flags >> (2 * c)) & 1u;
+    gg[c] = (flags >> (2 * c + 1)) & 1u;
+  }
+  float m = -1e38f;
+#pragma unroll
+  for (int c = 0; c < GS_CE_CHUNKS; c++)
+    if (vv[c]) m = fmaxf(m, x[c]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    m = fmaxf(m, __shfl_xor(m, off, SRX_WAVE));
+  float z = 0.f;
+#pragma unroll
+  for (int c = 0; c < GS_CE_CHUNKS; c++)
+    if (vv[c]) z += __expf(x[c] - m);
+  z = wave_reduce_sum(z);
+  const float logz = __logf(z) + m;
+  const float tgt = 1.f / (float)cnt;
+  float l = 0.f;
+#pragma unroll
+  for (int c = 0; c < GS_CE_CHUNKS; c++) {
+    const int a = lane + c * SRX_WAVE;
+    if (a >= A) continue;
+    float d = 0.f;
+    if (vv[c]) {
+      const float lp = x[c] - logz;  // log p
+      d = __expf(lp) - (gg[c] ? tgt : 0.f);
+      s.col[c] += d;
+      if (gg[c]) l -= tgt * lp;
+    }
+    Elem<T>::st(drow + a, d);
+  }
+  l = wave_reduce_sum(l);
+  s.loss += l;
+  s.count += 1.f;
+}
+
+// the wave's partial row: [0, A) column sums, [A] loss, [A + 1] row count
+__device__ __forceinline__ void gs_ce_flush(const GsCeAcc& s,
+                                            float* __restrict__ prow, int lane,
+                                            int A) {
+#pragma unroll
+  for (int c = 0; c < GS_CE_CHUNKS; c++) {
+    const int a = lane + c * SRX_WAVE;
+    if (a < A) prow[a] = s.col[c];
+  }
+  if (lane == 0) {
+    prow[A] = s.loss;
+    prow[A + 1] = s.count;
+  }
+}
+
+// out[b, c] = sum over rows [b R, min((b+1) R, n)) of in[:, c], added in row
+// order in fp64 and rounded to fp32 once (the mwe_colsum_kernel scheme):
+// applied until one row is left, it sums the per-wave rows without atomics.
+__global__ void gs_colsum_kernel(const float* __restrict__ in,
+                                 float* __restrict__ out, long n, int R,
+                                 int ncols) {
+  const int c = blockIdx.y * blockDim.x + threadIdx.x;
+  if (c >= ncols) return;
+  const long r0 = (long)blockIdx.x * R;
+  const long r1 = r0 + R < n ? r0 + R : n;
+  double s = 0.0;
+  for (long r = r0; r < r1; r++) s += (double)in[r * ncols + c];
+  out[(long)blockIdx.x * ncols + c] = (float)s;
+}
+
 // ---------------------------------------------------------------- parser
 // Actions: 0=SHIFT, 1=REDUCE, 2..2+L-1=LEFT-ARC(l), 2+L..2+2L-1=RIGHT-ARC(l)
-template <typename T, bool TRAIN>
+template <typename T, bool TRAIN, bool CE>
 __global__ __launch_bounds__(256) void gpu_arceager_kernel(
     const T* __restrict__ pre,       // [Tb+1, nF, HP]
     const int32_t* __restrict__ off,     // [n_docs] global token base
@@ -105,7 +218,8 @@ __global__ __launch_bounds__(256) void gpu_arceager_kernel(
     int32_t* __restrict__ head_out,   // flat [total] doc-local (-1 root)
     int32_t* __restrict__ label_out,  // flat [total]
     int32_t* __restrict__ steps_out,  // [1] total transitions (atomic)
-    long n_docs, long pad_row, int nF, int H, int A, int L) {
+    long n_docs, long pad_row, int nF, int H, int A, int L,
+    float* __restrict__ ce_part) {  // CE: [n_waves, A + 2] per-wave rows
   extern __shared__ char smem[];
   const int HP = 2 * H;
   T* Wlds = (T*)smem;                           // [A][GS_HPAD] row-major
@@ -144,6 +258,8 @@ __global__ __launch_bounds__(256) void gpu_arceager_kernel(
 
   const long wave_id = ((long)blockIdx.x * waves_per_block) + wslot;
   const long nwaves = (long)gridDim.x * waves_per_block;
+  GsCeAcc ce;
+  if (CE) gs_ce_init(ce);
   for (long d = wave_id; d < n_docs; d += nwaves) {
     const int n = lens[d];
     const long o = off[d];
@@ -257,6 +373,44 @@ __global__ __launch_bounds__(256) void gpu_arceager_kernel(
       const float eps = 1e-6f;
       float bg = -1e38f, bv = -1e38f;
       int ig = INT32_MAX, iv = INT32_MAX;
+      if constexpr (CE) {
+        // the row stays in registers over a fixed chunk count (no indexed
+        // arrays): rounded scores in x, valid / gold flags packed two bits
+        // per chunk; the argmax keeps the unrounded acc as below
+        float x[GS_CE_CHUNKS];
+        unsigned flags = 0;
+        int cnt = 0;
+#pragma unroll
+        for (int c = 0; c < GS_CE_CHUNKS; c++) {
+          x[c] = 0.f;
+          if (c * SRX_WAVE >= A) continue;  // wave-uniform
+          const int a = lane + c * SRX_WAVE;
+          bool valid = false, gold = false;
+          if (a < A) {
+            float acc = Blds[a] + gs_rowdot64<T>(Wlds + (size_t)a * GS_HPAD, my_hid);
+            if (a == 0) valid = v_shift;
+            else if (a == 1) valid = v_reduce;
+            else if (a < 2 + L) valid = v_la;
+            else valid = v_ra;
+            if (valid) {
+              float cost;
+              if (a == 0) cost = c_shift;
+              else if (a == 1) cost = c_reduce;
+              else if (a < 2 + L)
+                cost = c_la + ((la_gold >= 0 && (a - 2) != la_gold) ? 1.f : 0.f);
+              else
+                cost = c_ra + ((ra_gold >= 0 && (a - 2 - L) != ra_gold) ? 1.f : 0.f);
+              gold = cost <= cmin + eps;
+            }
+            x[c] = gs_round<T>(acc);
+            if (gold && (acc > bg || (acc == bg && a < ig))) { bg = acc; ig = a; }
+            if (valid && (acc > bv || (acc == bv && a < iv))) { bv = acc; iv = a; }
+          }
+          flags |= ((unsigned)valid | ((unsigned)gold << 1)) << (2 * c);
+          cnt += __popcll(__ballot(gold));
+        }
+        gs_ce_row<T>(x, flags, cnt, scores_a + arow * A, lane, A, ce);
+      } else {
       for (int a = lane; a < A; a += SRX_WAVE) {
         float acc = Blds[a] + gs_rowdot64<T>(Wlds + (size_t)a * GS_HPAD, my_hid);
         bool valid, gold = false;
@@ -282,6 +436,7 @@ __global__ __launch_bounds__(256) void gpu_arceager_kernel(
         bool sel = TRAIN ? gold : valid;
         if (sel && (acc > bg || (acc == bg && a < ig))) { bg = acc; ig = a; }
         if (valid && (acc > bv || (acc == bv && a < iv))) { bv = acc; iv = a; }
+      }
       }
 #pragma unroll
       for (int sh = 32; sh > 0; sh >>= 1) {
@@ -356,12 +511,14 @@ __global__ __launch_bounds__(256) void gpu_arceager_kernel(
     if (lane == 0) atomicAdd(steps_out, steps);
     __builtin_amdgcn_wave_barrier();
   }
+  if constexpr (CE)
+    gs_ce_flush(ce, ce_part + wave_id * (long)(A + 2), lane, A);
 }
 
 // ------------------------------------------------------------------- NER
 // Actions: 0=OUT; type t: 1+4t=B, 2+4t=I, 3+4t=L, 4+4t=U.  Gold codes per
 // token (-1 = missing).  One wave per doc; state is (i, open, open_start).
-template <typename T, bool TRAIN>
+template <typename T, bool TRAIN, bool CE>
 __global__ __launch_bounds__(256) void gpu_biluo_kernel(
     const T* __restrict__ pre, const int32_t* __restrict__ off,
     const int32_t* __restrict__ lens, const int32_t* __restrict__ gold,
@@ -371,7 +528,8 @@ __global__ __launch_bounds__(256) void gpu_biluo_kernel(
     uint8_t* __restrict__ valid_a, int64_t* __restrict__ feats_a,
     T* __restrict__ hidden_a, uint8_t* __restrict__ which_a,
     int32_t* __restrict__ tags_out, int32_t* __restrict__ steps_out,
-    long n_docs, long pad_row, int nF, int H, int A, int NT) {
+    long n_docs, long pad_row, int nF, int H, int A, int NT,
+    float* __restrict__ ce_part) {  // CE: [n_waves, A + 2] per-wave rows
   extern __shared__ char smem[];
   const int HP = 2 * H;
   T* Wlds = (T*)smem;                           // [A][GS_HPAD] row-major
@@ -393,6 +551,8 @@ __global__ __launch_bounds__(256) void gpu_biluo_kernel(
 
   const long wave_id = ((long)blockIdx.x * waves_per_block) + wslot;
   const long nwaves = (long)gridDim.x * waves_per_block;
+  GsCeAcc ce;
+  if (CE) gs_ce_init(ce);
   for (long d = wave_id; d < n_docs; d += nwaves) {
     const int n = lens[d];
     const long o = off[d];
@@ -429,6 +589,54 @@ __global__ __launch_bounds__(256) void gpu_biluo_kernel(
       int gcode = TRAIN ? gold[o + i] : -2;
       float bg = -1e38f, bv = -1e38f;
       int ig = INT32_MAX, iv = INT32_MAX;
+      if constexpr (CE) {
+        // as in gpu_arceager_kernel: the row stays in registers
+        float x[GS_CE_CHUNKS];
+        unsigned flags = 0;
+        int cnt = 0;
+#pragma unroll
+        for (int c = 0; c < GS_CE_CHUNKS; c++) {
+          x[c] = 0.f;
+          if (c * SRX_WAVE >= A) continue;  // wave-uniform
+          const int a = lane + c * SRX_WAVE;
+          bool valid = false, g = false;
+          if (a < A) {
+            float acc = Blds[a] + gs_rowdot64<T>(Wlds + (size_t)a * GS_HPAD, my_hid);
+            if (open < 0) {
+              if (a == 0) valid = true;                       // OUT
+              else {
+                int kind = (a - 1) % 4;
+                valid = (kind == 0) ? !last_tok : (kind == 3);  // B / U
+              }
+            } else {
+              int kind = (a - 1) % 4, t = (a - 1) / 4;
+              valid = t == open && ((kind == 1 && !last_tok) || kind == 2);  // I / L
+            }
+            if (TRAIN) {
+              if (gcode == -1) g = false;  // missing: no supervision
+              else if (gcode >= 0 && gcode < A) {
+                // gold action valid? then one-hot; else uniform over valid
+                bool gv;
+                if (open < 0)
+                  gv = gcode == 0 ||
+                       ((gcode - 1) % 4 == 0 && !last_tok) || ((gcode - 1) % 4 == 3);
+                else
+                  gv = (gcode - 1) / 4 == open &&
+                       (((gcode - 1) % 4 == 1 && !last_tok) || (gcode - 1) % 4 == 2);
+                g = gv ? (a == gcode) : valid;
+              } else {
+                g = valid;
+              }
+            }
+            x[c] = gs_round<T>(acc);
+            if (g && (acc > bg || (acc == bg && a < ig))) { bg = acc; ig = a; }
+            if (valid && (acc > bv || (acc == bv && a < iv))) { bv = acc; iv = a; }
+          }
+          flags |= ((unsigned)valid | ((unsigned)g << 1)) << (2 * c);
+          cnt += __popcll(__ballot(g));
+        }
+        gs_ce_row<T>(x, flags, cnt, scores_a + arow * A, lane, A, ce);
+      } else {
       for (int a = lane; a < A; a += SRX_WAVE) {
         float acc = Blds[a] + gs_rowdot64<T>(Wlds + (size_t)a * GS_HPAD, my_hid);
         bool valid;
@@ -468,6 +676,7 @@ __global__ __launch_bounds__(256) void gpu_biluo_kernel(
         if (sel && (acc > bg || (acc == bg && a < ig))) { bg = acc; ig = a; }
         if (valid && (acc > bv || (acc == bv && a < iv))) { bv = acc; iv = a; }
       }
+      }
 #pragma unroll
       for (int sh = 32; sh > 0; sh >>= 1) {
         float obg = __shfl_xor(bg, sh, SRX_WAVE);
@@ -494,18 +703,42 @@ __global__ __launch_bounds__(256) void gpu_biluo_kernel(
     }
     if (lane == 0) atomicAdd(steps_out, n);
   }
+  if constexpr (CE)
+    gs_ce_flush(ce, ce_part + wave_id * (long)(A + 2), lane, A);
+}
+
+// Fold the per-wave CE rows [n, A + 2] into one row (64 rows per block per
+// level, in row order) -> {loss_count [2], colsum [A]}
+std::vector<at::Tensor> gs_ce_finish(at::Tensor part, int A,
+                                     hipStream_t stream) {
+  const int ncols = A + 2;
+  long n = part.size(0);
+  const int R = 64;
+  do {
+    long nb = (n + R - 1) / R;
+    auto out = at::empty({nb, (long)ncols}, part.options());
+    hipLaunchKernelGGL(gs_colsum_kernel, dim3((unsigned)nb, (ncols + 63) / 64),
+                       dim3(64), 0, stream, part.data_ptr<float>(),
+                       out.data_ptr<float>(), n, R, ncols);
+    part = out;
+    n = nb;
+  } while (n > 1);
+  auto sums = part.view({(long)ncols});
+  return {sums.narrow(0, A, 2), sums.narrow(0, 0, A)};
 }
 
 }  // namespace
 
 // ----------------------------------------------------------------- hosts
 // Returns {scores, gold, valid, feats, which, hidden, heads, labels, steps}
-// (arenas empty for decode).
+// (arenas empty for decode).  train && fuse_ce (A <= 256): the first tensor
+// is dScores, gold / valid come back empty [0, A] (never allocated), and
+// {loss_count [2], colsum [A]} (transition_ce's returns) are appended.
 std::vector<at::Tensor> srx_gpu_arceager(
     at::Tensor pre, at::Tensor off, at::Tensor lens, at::Tensor gh,
     at::Tensor gl, at::Tensor kids_off, at::Tensor kids, at::Tensor lowerB,
     at::Tensor upperW, at::Tensor upperB, int64_t total, int64_t n_labels,
-    bool train) {
+    bool train, bool fuse_ce) {
   TORCH_CHECK(pre.is_cuda() && pre.is_contiguous());
   long n_docs = off.size(0);
   int H = (int)pre.size(-1) / 2;
@@ -513,6 +746,8 @@ std::vector<at::Tensor> srx_gpu_arceager(
   long pad_row = pre.size(0) - 1;
   TORCH_CHECK(H <= 64, "gpu state machine supports H <= 64");
   TORCH_CHECK((size_t)A * 72 * pre.element_size() <= 96 * 1024, "upper too large");
+  const bool ce = train && fuse_ce;
+  TORCH_CHECK(!ce || A <= 64 * GS_CE_CHUNKS, "fused CE supports A <= 256");
   auto opt = pre.options();
   auto optb = opt.dtype(at::kByte);
   auto opti = opt.dtype(at::kInt);
@@ -522,8 +757,8 @@ std::vector<at::Tensor> srx_gpu_arceager(
   at::Tensor scores_a, gold_a, valid_a, feats_a, hidden_a, which_a;
   if (train) {
     scores_a = at::zeros({cap, (long)A}, opt);
-    gold_a = at::zeros({cap, (long)A}, optb);
-    valid_a = at::zeros({cap, (long)A}, optb);
+    gold_a = ce ? at::empty({0, (long)A}, optb) : at::zeros({cap, (long)A}, optb);
+    valid_a = ce ? at::empty({0, (long)A}, optb) : at::zeros({cap, (long)A}, optb);
     feats_a = at::full({cap, 13L}, pad_row, opt.dtype(at::kLong));
     hidden_a = at::zeros({cap, (long)H}, opt);
     which_a = at::zeros({cap, (long)H}, optb);
@@ -550,8 +785,14 @@ std::vector<at::Tensor> srx_gpu_arceager(
   int grid = (int)std::min<long>((n_docs + waves_per_block - 1) / waves_per_block,
                                  16384);
   grid = std::max(grid, 1);
-#define LAUNCH_AE(T_, TR)                                                     \
-  hipLaunchKernelGGL((gpu_arceager_kernel<T_, TR>), dim3(grid), dim3(block),  \
+  // every wave of the grid writes its whole row: no fill needed
+  at::Tensor ce_part;
+  if (ce)
+    ce_part = at::empty({(long)grid * waves_per_block, (long)A + 2},
+                        opt.dtype(at::kFloat));
+#define LAUNCH_AE(T_, TR, CE_)                                                \
+  hipLaunchKernelGGL((gpu_arceager_kernel<T_, TR, CE_>), dim3(grid),          \
+                     dim3(block),                                             \
                      lds, stream, (const T_*)pre.data_ptr(),                  \
                      off.data_ptr<int32_t>(), lens.data_ptr<int32_t>(),       \
                      gh.numel() ? gh.data_ptr<int32_t>() : nullptr,           \
@@ -568,32 +809,50 @@ std::vector<at::Tensor> srx_gpu_arceager(
                      which_a.numel() ? which_a.data_ptr<uint8_t>() : nullptr, \
                      heads.data_ptr<int32_t>(), labels.data_ptr<int32_t>(),   \
                      steps.data_ptr<int32_t>(), n_docs, pad_row, 13, H, A,    \
-                     (int)n_labels)
+                     (int)n_labels,                                           \
+                     CE_ ? ce_part.data_ptr<float>() : nullptr)
   static std::once_flag attr_ae;
   std::call_once(attr_ae, [&]() {
-    (void)hipFuncSetAttribute((const void*)gpu_arceager_kernel<bf16_t, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)gpu_arceager_kernel<bf16_t, false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)gpu_arceager_kernel<float, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute((const void*)gpu_arceager_kernel<float, false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    (void)hipFuncSetAttribute(
+        (const void*)gpu_arceager_kernel<bf16_t, true, false>,
+        hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    (void)hipFuncSetAttribute(
+        (const void*)gpu_arceager_kernel<bf16_t, true, true>,
+        hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    (void)hipFuncSetAttribute(
+        (const void*)gpu_arceager_kernel<bf16_t, false, false>,
+        hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    (void)hipFuncSetAttribute(
+        (const void*)gpu_arceager_kernel<float, true, false>,
+        hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    (void)hipFuncSetAttribute(
+        (const void*)gpu_arceager_kernel<float, true, true>,
+        hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    (void)hipFuncSetAttribute(
+        (const void*)gpu_arceager_kernel<float, false, false>,
+        hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
   });
   if (pre.scalar_type() == at::kBFloat16) {
-    if (train) LAUNCH_AE(bf16_t, true); else LAUNCH_AE(bf16_t, false);
+    if (ce) LAUNCH_AE(bf16_t, true, true);
+    else if (train) LAUNCH_AE(bf16_t, true, false);
+    else LAUNCH_AE(bf16_t, false, false);
   } else {
-    if (train) LAUNCH_AE(float, true); else LAUNCH_AE(float, false);
+    if (ce) LAUNCH_AE(float, true, true);
+    else if (train) LAUNCH_AE(float, true, false);
+    else LAUNCH_AE(float, false, false);
   }
 #undef LAUNCH_AE
-  return {scores_a, gold_a, valid_a, feats_a, which_a, hidden_a, heads,
-          labels, steps};
+  std::vector<at::Tensor> outs = {scores_a, gold_a, valid_a, feats_a, which_a,
+                                  hidden_a, heads, labels, steps};
+  if (ce)
+    for (auto& t : gs_ce_finish(ce_part, A, stream)) outs.push_back(t);
+  return outs;
 }
 
 std::vector<at::Tensor> srx_gpu_biluo(
     at::Tensor pre, at::Tensor off, at::Tensor lens, at::Tensor gold,
     at::Tensor lowerB, at::Tensor upperW, at::Tensor upperB,
-    int64_t total, int64_t n_types, bool train) {
+    int64_t total, int64_t n_types, bool train, bool fuse_ce) {
   TORCH_CHECK(pre.is_cuda() && pre.is_contiguous());
   long n_docs = off.size(0);
   int H = (int)pre.size(-1) / 2;
@@ -601,6 +860,8 @@ std::vector<at::Tensor> srx_gpu_biluo(
   long pad_row = pre.size(0) - 1;
   TORCH_CHECK(H <= 64, "gpu state machine supports H <= 64");
   TORCH_CHECK((size_t)A * 72 * pre.element_size() <= 96 * 1024, "upper too large");
+  const bool ce = train && fuse_ce;
+  TORCH_CHECK(!ce || A <= 64 * GS_CE_CHUNKS, "fused CE supports A <= 256");
   auto opt = pre.options();
   auto optb = opt.dtype(at::kByte);
   auto opti = opt.dtype(at::kInt);
@@ -609,8 +870,8 @@ std::vector<at::Tensor> srx_gpu_biluo(
   at::Tensor scores_a, gold_a, valid_a, feats_a, hidden_a, which_a;
   if (train) {
     scores_a = at::zeros({cap, (long)A}, opt);
-    gold_a = at::zeros({cap, (long)A}, optb);
-    valid_a = at::zeros({cap, (long)A}, optb);
+    gold_a = ce ? at::empty({0, (long)A}, optb) : at::zeros({cap, (long)A}, optb);
+    valid_a = ce ? at::empty({0, (long)A}, optb) : at::zeros({cap, (long)A}, optb);
     feats_a = at::full({cap, 6L}, pad_row, opt.dtype(at::kLong));
     hidden_a = at::zeros({cap, (long)H}, opt);
     which_a = at::zeros({cap, (long)H}, optb);
@@ -633,8 +894,12 @@ std::vector<at::Tensor> srx_gpu_biluo(
   int grid = (int)std::min<long>((n_docs + waves_per_block - 1) / waves_per_block,
                                  16384);
   grid = std::max(grid, 1);
-#define LAUNCH_BI(T_, TR)                                                     \
-  hipLaunchKernelGGL((gpu_biluo_kernel<T_, TR>), dim3(grid), dim3(block),     \
+  at::Tensor ce_part;
+  if (ce)
+    ce_part = at::empty({(long)grid * waves_per_block, (long)A + 2},
+                        opt.dtype(at::kFloat));
+#define LAUNCH_BI(T_, TR, CE_)                                                \
+  hipLaunchKernelGGL((gpu_biluo_kernel<T_, TR, CE_>), dim3(grid), dim3(block), \
                      lds, stream, (const T_*)pre.data_ptr(),                  \
                      off.data_ptr<int32_t>(), lens.data_ptr<int32_t>(),       \
                      gold.numel() ? gold.data_ptr<int32_t>() : nullptr,       \
@@ -647,12 +912,21 @@ std::vector<at::Tensor> srx_gpu_biluo(
                      (T_*)hidden_a.data_ptr(),                                \
                      which_a.numel() ? which_a.data_ptr<uint8_t>() : nullptr, \
                      tags.data_ptr<int32_t>(), steps.data_ptr<int32_t>(),     \
-                     n_docs, pad_row, 6, H, A, (int)n_types)
+                     n_docs, pad_row, 6, H, A, (int)n_types,                  \
+                     CE_ ? ce_part.data_ptr<float>() : nullptr)
   if (pre.scalar_type() == at::kBFloat16) {
-    if (train) LAUNCH_BI(bf16_t, true); else LAUNCH_BI(bf16_t, false);
+    if (ce) LAUNCH_BI(bf16_t, true, true);
+    else if (train) LAUNCH_BI(bf16_t, true, false);
+    else LAUNCH_BI(bf16_t, false, false);
   } else {
-    if (train) LAUNCH_BI(float, true); else LAUNCH_BI(float, false);
+    if (ce) LAUNCH_BI(float, true, true);
+    else if (train) LAUNCH_BI(float, true, false);
+    else LAUNCH_BI(float, false, false);
   }
 #undef LAUNCH_BI
-  return {scores_a, gold_a, valid_a, feats_a, which_a, hidden_a, tags, steps};
+  std::vector<at::Tensor> outs = {scores_a, gold_a, valid_a, feats_a, which_a,
+                                  hidden_a, tags, steps};
+  if (ce)
+    for (auto& t : gs_ce_finish(ce_part, A, stream)) outs.push_back(t);
+  return outs;
 }

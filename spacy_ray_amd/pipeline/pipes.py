@@ -271,7 +271,7 @@ class _TransitionTask:
                  "dPre32", "hip", "score_chunks", "gold_chunks",
                  "valid_chunks", "n_states_total", "entries", "fused",
                  "task_id", "cpp", "cpp_outs", "gpu", "gpu_decode",
-                 "steps_dev")
+                 "steps_dev", "ce_fused")
 
     def __init__(self, pipe, shards, t2v, train: bool) -> None:
         from spacy_ray_amd.ops import api as _ops
@@ -321,6 +321,9 @@ class _TransitionTask:
         self.gpu: Optional[Dict] = None
         self.gpu_decode = None
         self.steps_dev: Optional[torch.Tensor] = None
+        # (loss_count, colsum) when the state machine ran the CE in-kernel
+        # (fuse_ce): cpp_outs[0][0] is then dScores, not the scores
+        self.ce_fused = None
 
     def launch(self, states):
         from spacy_ray_amd.ops import api as _ops
@@ -566,7 +569,8 @@ class _TransitionPipeBase(TrainablePipe):
                 scores, gold, valid, feats, which, hidden = (
                     torch.cat(c, dim=0) for c in zip(*outs)
                 )
-            from spacy_ray_amd.ops.api import transition_loop_loss
+            from spacy_ray_amd.ops.api import (transition_loop_loss,
+                                               transition_loop_loss_fused)
 
             mod = self.module
             lkw = {}
@@ -576,10 +580,19 @@ class _TransitionPipeBase(TrainablePipe):
                            maxlen=task.gpu["maxlen"],
                            doc_total=task.gpu["total"])
             with timing.span("raw/loss_build"):
-                loss = transition_loop_loss(
-                    task.pre, mod.lower_b, mod.upper.weight, mod.upper.bias,
-                    scores, gold, valid, feats, which, hidden, **lkw,
-                )
+                if task.ce_fused is not None:
+                    loss_count, colsum = task.ce_fused
+                    loss = transition_loop_loss_fused(
+                        task.pre, mod.lower_b, mod.upper.weight,
+                        mod.upper.bias, scores, colsum, loss_count, feats,
+                        which, hidden, **lkw,
+                    )
+                else:
+                    loss = transition_loop_loss(
+                        task.pre, mod.lower_b, mod.upper.weight,
+                        mod.upper.bias, scores, gold, valid, feats, which,
+                        hidden, **lkw,
+                    )
                 if task.steps_dev is not None:
                     # GPU state machine: arenas are CAPACITY-sized (unused
                     # rows masked out of the CE); normalize by the REAL
@@ -651,8 +664,10 @@ class _TransitionPipeBase(TrainablePipe):
     # doc — state, dynamic oracle, scorer and argmax all in LDS/registers),
     # replacing the per-step host round trips of the C++ loop.  Train
     # returns the same arenas the host loop produces, so the batched CE
-    # backward is shared; decode returns heads/labels (or BILUO tags)
-    # directly.  SRX_GPU_STATES=0 reverts to the host loop.
+    # backward is shared (by default the CE itself runs in-kernel and the
+    # scores arena comes back as dScores: _fuse_ce); decode returns
+    # heads/labels (or BILUO tags) directly.  SRX_GPU_STATES=0 reverts to
+    # the host loop.
     def _gpu_ready(self, lengths, t2v) -> bool:
         if not t2v.is_cuda or os.environ.get("SRX_GPU_STATES", "1") != "1":
             return False
@@ -673,6 +688,14 @@ class _TransitionPipeBase(TrainablePipe):
 
     def _gpu_launch(self, task) -> None:
         raise NotImplementedError
+
+    def _fuse_ce(self) -> bool:
+        """Training launches run the transition CE inside the state machine
+        (the first arena is then dScores); SRX_FUSED_CE=0, deterministic
+        mode and A > 256 keep the separate transition_ce pass."""
+        from spacy_ray_amd.ops.api import fused_ce_enabled
+
+        return fused_ce_enabled(self._n_actions())
 
     def _maybe_gpu_task(self, staged, lengths, t2v, batch, train):
         """Build a GPU-state-machine task if supported, else None."""
@@ -926,15 +949,18 @@ class ParserPipe(_TransitionPipeBase):
     def _gpu_launch(self, task) -> None:
         g = task.gpu
         mod = self.module
+        fuse_ce = task.train and self._fuse_ce()
         outs = task.hip.gpu_arceager(
             task.pre_d.contiguous(), g["off"], g["lens"], g["gh"], g["gl"],
             g["kids_off"], g["kids"], mod.lower_b.detach(),
             mod.upper.weight.detach(), mod.upper.bias.detach(), g["total"],
-            len(self.labels), task.train,
+            len(self.labels), task.train, fuse_ce=fuse_ce,
         )
         if task.train:
             task.cpp_outs.append(list(outs[:6]))
             task.steps_dev = outs[8]
+            if fuse_ce:
+                task.ce_fused = (outs[9], outs[10])
         else:
             task.gpu_decode = (outs[6], outs[7])
 
@@ -1041,14 +1067,18 @@ class NerPipe(_TransitionPipeBase):
     def _gpu_launch(self, task) -> None:
         g = task.gpu
         mod = self.module
+        fuse_ce = task.train and self._fuse_ce()
         outs = task.hip.gpu_biluo(
             task.pre_d.contiguous(), g["off"], g["lens"], g["gold"],
             mod.lower_b.detach(), mod.upper.weight.detach(),
             mod.upper.bias.detach(), g["total"], len(self.labels), task.train,
+            fuse_ce=fuse_ce,
         )
         if task.train:
             task.cpp_outs.append(list(outs[:6]))
             task.steps_dev = outs[7]
+            if fuse_ce:
+                task.ce_fused = (outs[8], outs[9])
         else:
             task.gpu_decode = outs[6]
 

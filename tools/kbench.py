@@ -156,6 +156,11 @@ def bench_gpustate():
     timeit("gpu_arceager train (50k docs)",
            lambda: hip.gpu_arceager(pre, off, lens, gh, gl, kids_off, kids,
                                     lowerB, upperW, upperB, T, nL, True))
+    # same shapes: compare against the train line plus transition_ce
+    timeit("gpu_arceager train fused-CE (50k docs)",
+           lambda: hip.gpu_arceager(pre, off, lens, gh, gl, kids_off, kids,
+                                    lowerB, upperW, upperB, T, nL, True,
+                                    fuse_ce=True))
     timeit("gpu_arceager decode (50k docs)",
            lambda: hip.gpu_arceager(pre, off, lens, gh, gl, kids_off, kids,
                                     lowerB, upperW, upperB, T, nL, False))
@@ -167,6 +172,9 @@ def bench_gpustate():
     timeit("gpu_biluo train (50k docs)",
            lambda: hip.gpu_biluo(pre6, off, lens, gold, lowerB, upW2, upB2,
                                  T, 18, True))
+    timeit("gpu_biluo train fused-CE (50k docs)",
+           lambda: hip.gpu_biluo(pre6, off, lens, gold, lowerB, upW2, upB2,
+                                 T, 18, True, fuse_ce=True))
 
 
 def bench_attn():
