@@ -186,6 +186,7 @@ def init_config_cli(
     arch: str = typer.Option("cnn", "--arch", help="tok2vec architecture: cnn | trf"),
     width: int = typer.Option(0, "--width", help="tok2vec width (default: 96 cnn / 768 trf)"),
     gpu: bool = typer.Option(False, "--gpu", help="Tune defaults for GPU training"),
+    vectors: str = typer.Option("", "--vectors", help="Pipeline directory from `init vectors`: use static vectors"),
 ):
     """Generate a ready-to-train config (the `spacy init config` role)."""
     from spacy_ray_amd.cli.templates import render_config
@@ -197,13 +198,35 @@ def init_config_cli(
             "spancat", "entity_ruler", "attribute_ruler", "lemmatizer")]
     if bad:
         raise SystemExit(f"unknown pipeline components: {bad}")
-    text = render_config(lang=lang, pipes=pipes, arch=arch, width=width, gpu=gpu)
+    text = render_config(lang=lang, pipes=pipes, arch=arch, width=width, gpu=gpu,
+                         vectors=vectors)
     if str(output_path) == "-":
         print(text)
     else:
         output_path.write_text(text)
         print(f"[+] wrote {output_path} — train with: "
               f"spacy-mi ray train {output_path} --output ./model")
+
+
+@init_app.command("vectors")
+def init_vectors_cli(
+    lang: str = typer.Argument(..., help="Language code of the pipeline"),
+    vectors_loc: Path = typer.Argument(..., help="word2vec text file (.txt or .txt.gz)"),
+    output_dir: Path = typer.Argument(..., help="Pipeline directory to write"),
+    truncate: int = typer.Option(0, "--truncate", "-t", help="Keep only the first N vectors (0 = all)"),
+    name: str = typer.Option("", "--name", "-n", help="Name of the table (default: <lang>_vectors)"),
+):
+    """Convert word vectors to a loadable pipeline directory that holds only
+    a vocab with vectors (the `spacy init vectors` role).  Point
+    [initialize] vectors (or [paths] vectors) at the output."""
+    from spacy_ray_amd.pipeline.language import init_vectors
+
+    try:
+        nlp = init_vectors(lang, vectors_loc, output_dir, truncate=truncate,
+                           name=name or None)
+    except ValueError as e:
+        raise SystemExit(f"[x] {e}")
+    print(f"[+] wrote {output_dir}: {nlp.vocab.vectors!r}")
 
 
 debug_app = typer.Typer(name="debug", no_args_is_help=True,
@@ -237,6 +260,10 @@ def debug_config_cli(
     icfg = config.interpolate()
     T = resolve(icfg.get("training", {}), schema=ConfigSchemaTraining)
     nlp = build_nlp(config)
+    from spacy_ray_amd.pipeline.language import check_static_vectors_config
+
+    for line in check_static_vectors_config(icfg):
+        print(f"[+] {line}")
     print(f"[+] config OK: pipeline {nlp.pipe_names}")
     print(f"[+] training resolved: optimizer={type(T['optimizer']).__name__}, "
           f"max_steps={T.get('max_steps')}, eval_frequency={T.get('eval_frequency')}, "

@@ -102,6 +102,9 @@ def component_to_thinc_nodes(pipe) -> List[Tuple[str, Dict[str, np.ndarray]]]:
         nodes.append(("multihashembed", {}))
         for i, table in enumerate(embed.tables):
             nodes.append((f"hashembed>>{embed.attrs[i]}", {"E": npf(table)}))
+        if getattr(embed, "static_vectors", None) is not None:
+            # only the projection: the vector table lives in the vocab
+            nodes.append(("static_vectors", {"W": npf(embed.static_vectors.W)}))
         nodes.append(("maxout", {"W": npf(embed.mixer.weight),
                                  "b": npf(embed.mixer.bias)}))
         nodes.append(("layernorm", {"G": npf(embed.mixer.norm.weight),
@@ -145,6 +148,8 @@ def load_thinc_nodes_into_component(pipe, data: bytes) -> int:
             embed = enc.embed
             for i, table in enumerate(embed.tables):
                 out.append((f"hashembed>>{embed.attrs[i]}", "E", table))
+            if getattr(embed, "static_vectors", None) is not None:
+                out.append(("static_vectors", "W", embed.static_vectors.W))
             out.append(("maxout", "W", embed.mixer.weight))
             out.append(("maxout", "b", embed.mixer.bias))
             out.append(("layernorm", "G", embed.mixer.norm.weight))

@@ -7,6 +7,7 @@ shape-inference-on-sample initialization (`/root/reference/spacy_ray/
 worker.py:91` init_nlp contract)."""
 from __future__ import annotations
 
+import contextlib
 from typing import List, Optional
 
 from spacy_ray_amd.config.registry import registry
@@ -34,10 +35,40 @@ def make_multi_hash_embed(
     include_static_vectors: bool = False,
     seed: int = 0,
 ):
-    if include_static_vectors:
-        raise NotImplementedError("static vectors are not supported (no pretrained vectors offline)")
-    return ModelSpec(lambda: MultiHashEmbed(width, rows=list(rows), attrs=list(attrs), seed=seed),
-                     width=width, kind="embed")
+    def build():
+        return MultiHashEmbed(
+            width, rows=list(rows), attrs=list(attrs), seed=seed,
+            include_static_vectors=include_static_vectors,
+            vocab=_vocab_for_build() if include_static_vectors else None)
+
+    return ModelSpec(build, width=width, kind="embed")
+
+
+# Modules are built inside pipe.initialize / pipe.load_cfg, which know no
+# vocab; Language wraps those calls in `building_for(vocab)` so that a
+# StaticVectors layer can size its projection from the loaded table.
+_BUILD_VOCAB: list = []
+
+
+@contextlib.contextmanager
+def building_for(vocab):
+    _BUILD_VOCAB.append(vocab)
+    try:
+        yield
+    finally:
+        _BUILD_VOCAB.pop()
+
+
+def _vocab_for_build():
+    vocab = _BUILD_VOCAB[-1] if _BUILD_VOCAB else None
+    vectors = getattr(vocab, "vectors", None)
+    if vectors is None:
+        raise ValueError(
+            "include_static_vectors = true but no vectors are loaded: set "
+            "[initialize] vectors (or [paths] vectors) to a directory "
+            "written by `spacy-mi init vectors`, or set "
+            "include_static_vectors = false")
+    return vocab
 
 
 @registry.architectures("spacy.MaxoutWindowEncoder.v2")
@@ -70,9 +101,15 @@ def make_hash_embed_cnn(
     rows = [embed_size, embed_size // 2, embed_size // 2, embed_size // 2] if subword_features else [embed_size]
     attrs = ["NORM", "PREFIX", "SUFFIX", "SHAPE"] if subword_features else ["NORM"]
 
+    # spaCy's HashEmbedCNN: any non-null `pretrained_vectors` turns the
+    # static-vectors block on; the table itself comes from the vocab
+    static = bool(pretrained_vectors)
+
     def build():
         return Tok2Vec(
-            MultiHashEmbed(width, rows=rows, attrs=attrs),
+            MultiHashEmbed(width, rows=rows, attrs=attrs,
+                           include_static_vectors=static,
+                           vocab=_vocab_for_build() if static else None),
             MaxoutWindowEncoder(width, depth=depth, window_size=window_size,
                                 maxout_pieces=maxout_pieces),
         )

@@ -17,7 +17,7 @@ from spacy_ray_amd.vocab.doc import Doc
 
 class TokenBatch:
     __slots__ = ("attr_ids", "lengths", "n_tokens", "n_real_tokens", "docs",
-                 "staged", "lengths_np")
+                 "staged", "lengths_np", "vec_rows", "vec_rows_attr")
 
     def __init__(self, docs: Sequence[Doc], device: torch.device,
                  pad_to: int = 0):
@@ -64,6 +64,36 @@ class TokenBatch:
         # the step blocks the host behind every queued kernel.  Replayed
         # batches (bench) keep the cache across steps.
         self.staged = {}
+        # static vectors: one int32 [T] row tensor (-1 = OOV and pad rows),
+        # shipped only when the vocab has a table AND a model asked for it
+        self.vec_rows = None
+        self.vec_rows_attr = None
+        vocab = self.docs[0].vocab if self.docs else None
+        if (vocab is not None and getattr(vocab, "vectors", None) is not None
+                and vocab.vector_key_attrs):
+            self.vec_rows_attr = vocab.vector_key_attrs[0]
+            self.vec_rows = self._build_vec_rows(self.vec_rows_attr)
+
+    def _build_vec_rows(self, key_attr: str) -> torch.Tensor:
+        from spacy_ray_amd.utils.pinned import to_device
+
+        parts = [d.get_vector_rows(key_attr) for d in self.docs]
+        n_pad = self.n_tokens - self.n_real_tokens
+        if n_pad > 0:
+            parts.append(np.full(n_pad, -1, dtype=np.int32))
+        rows = (np.concatenate(parts) if parts
+                else np.zeros(0, dtype=np.int32)).astype(np.int32, copy=False)
+        return to_device(rows, self.attr_ids.device)
+
+    def get_vec_rows(self, key_attr: str) -> torch.Tensor:
+        """Vector rows under `key_attr`; the tensor built at construction
+        when it matches, otherwise built once and kept in `staged`."""
+        if self.vec_rows is not None and key_attr == self.vec_rows_attr:
+            return self.vec_rows
+        key = ("vec_rows", key_attr)
+        if key not in self.staged:
+            self.staged[key] = self._build_vec_rows(key_attr)
+        return self.staged[key]
 
     def __len__(self) -> int:
         return len(self.docs)

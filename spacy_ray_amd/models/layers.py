@@ -50,6 +50,42 @@ class LayerNorm(nn.Module):
         return ops.layernorm(X, self.weight, self.bias, self.eps)
 
 
+class StaticVectors(nn.Module):
+    """spaCy's StaticVectors layer: vectors[rows] @ W^T.  One trainable
+    projection `W` [nO, nM], Glorot-initialised; no bias, no dropout.  The
+    output row is zero for out-of-vocabulary tokens and the pad pseudo-doc.
+
+    The vector table itself is NOT part of the module: `vectors` is the
+    vocab's Vectors object (a plain attribute, so it is in no state_dict,
+    parameter list or gradient bucket), and its device copy is shared by
+    every layer that uses it."""
+
+    def __init__(self, nO: int, nM: int, key_attr: str = "ORTH", vectors=None):
+        super().__init__()
+        self.nO, self.nM, self.key_attr = nO, nM, key_attr
+        self.W = nn.Parameter(glorot_uniform_(torch.empty(nO, nM)))
+        self.__dict__["vectors"] = vectors
+
+    def bind(self, vectors) -> None:
+        if vectors.width != self.nM:
+            raise ValueError(
+                f"StaticVectors was built for {self.nM}-dimensional vectors "
+                f"but the vocab's table {vectors.name!r} has width "
+                f"{vectors.width}")
+        self.__dict__["vectors"] = vectors
+
+    def table(self) -> torch.Tensor:
+        if self.vectors is None:
+            raise ValueError(
+                "StaticVectors has no vector table: load one into "
+                "nlp.vocab.vectors ([initialize] vectors = <path>)")
+        return self.vectors.device_table(self.W.device, self.W.dtype)
+
+    def forward(self, batch) -> torch.Tensor:
+        return ops.static_vectors(self.W, self.table(),
+                                  batch.get_vec_rows(self.key_attr))
+
+
 class Linear(nn.Module):
     def __init__(self, nI: int, nO: int, bias: bool = True):
         super().__init__()

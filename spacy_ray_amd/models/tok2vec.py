@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from spacy_ray_amd.ops import api as ops
 from .batch import TokenBatch
-from .layers import LayerNorm, Maxout
+from .layers import LayerNorm, Maxout, StaticVectors
 
 
 class MultiHashEmbed(nn.Module):
@@ -24,7 +24,14 @@ class MultiHashEmbed(nn.Module):
         rows: List[int] = (5000, 2500, 2500, 2500),
         attrs: List[str] = ("NORM", "PREFIX", "SUFFIX", "SHAPE"),
         seed: int = 0,
+        include_static_vectors: bool = False,
+        vocab=None,
+        key_attr: Optional[str] = None,
     ):
+        """include_static_vectors: one more column block, the projection of
+        `vocab.vectors` (StaticVectors), LAST in the mixer input.  Without
+        it the module is exactly the no-vectors one (same parameters, same
+        RNG draws, same state_dict keys)."""
         super().__init__()
         assert len(rows) == len(attrs)
         self.width = width
@@ -34,13 +41,32 @@ class MultiHashEmbed(nn.Module):
             nn.Parameter(torch.randn(r, width) * (1.0 / (width ** 0.5)))
             for r in rows
         )
-        self.mixer = Maxout(width * len(attrs), width, pieces=3, normalize=True)
+        n_blocks = len(attrs) + (1 if include_static_vectors else 0)
+        self.mixer = Maxout(width * n_blocks, width, pieces=3, normalize=True)
+        if include_static_vectors:
+            vectors = getattr(vocab, "vectors", None)
+            if vectors is None:
+                raise ValueError(
+                    "include_static_vectors = true needs a vocab with vectors "
+                    "([initialize] vectors = <path>)")
+            key_attr = key_attr or vectors.key_attr
+            self.static_vectors = StaticVectors(width, vectors.width,
+                                                key_attr=key_attr, vectors=vectors)
+            if key_attr not in vocab.vector_key_attrs:
+                vocab.vector_key_attrs.append(key_attr)
+        else:
+            self.static_vectors = None
 
     def forward(self, batch: TokenBatch, drop: float = 0.0) -> torch.Tensor:
         from spacy_ray_amd.utils import timing
 
         with timing.phase("t2v/embed_tables"):
-            X = ops.multi_hashembed(batch.attr_ids, self.seeds, list(self.tables))
+            sv = self.static_vectors
+            vectors = None
+            if sv is not None:
+                vectors = (sv.table(), batch.get_vec_rows(sv.key_attr), sv.W)
+            X = ops.multi_hashembed(batch.attr_ids, self.seeds,
+                                    list(self.tables), vectors)
         with timing.phase("t2v/mixer_gemm"):
             Y = ops.linear_cdw(X, self.mixer.weight, self.mixer.bias)
         with timing.phase("t2v/mixer_maxout"):

@@ -223,14 +223,170 @@ class _MultiHashEmbed(torch.autograd.Function):
         return (None, None, *grads)
 
 
-def multi_hashembed(ids4: torch.Tensor, seeds, tables) -> torch.Tensor:
+def multi_hashembed(ids4: torch.Tensor, seeds, tables, vectors=None) -> torch.Tensor:
     """GPU fast path for MultiHashEmbed; CPU falls back to per-table
-    hashembed + cat."""
+    hashembed + cat.  `vectors` = (table, rows, W) appends the static
+    vectors projection as the last column block."""
+    if vectors is not None:
+        return multi_hashembed_vectors(ids4, seeds, tables, *vectors)
     if ids4.is_cuda and _want_hip(tables[0]):
         return _MultiHashEmbed.apply(ids4, list(seeds), *tables)
     outs = [hashembed(t, ids4[:, i].contiguous(), int(seeds[i]))
             for i, t in enumerate(tables)]
     return torch.cat(outs, dim=1)
+
+
+# --------------------------------------------------------- static vectors
+# Fused gather-project kernels (srx_staticvec.hip.h) against the composed
+# path (index_select + mm): the fused path is the default only where the
+# tools/kbench.py measurement found it not slower (profiles/README.md);
+# SRX_STATIC_VECTORS=fused / composed overrides the default either way.
+# Measured (T = 1M, nM = 300): forward 0.49 ms against 1.14 ms, dW 0.32 ms
+# against 2.89 ms at nO = 96; 0.53 / 1.14 and 0.31 / 2.75 ms at nO = 128.
+STATIC_VECTORS_FUSED_DEFAULT = True
+
+
+def static_vectors_available(table: torch.Tensor, W: torch.Tensor) -> bool:
+    """The fused kernels need the bf16 padded table ([V, nMp], nMp =
+    roundup(nM, 32) <= 320), a bf16 W with nO in (96, 128), and the
+    extension."""
+    nMp = table.shape[1]
+    return (
+        table.is_cuda
+        and W.is_cuda
+        and table.dtype == torch.bfloat16
+        and W.dtype == torch.bfloat16
+        and W.shape[0] in (96, 128)
+        and nMp % 32 == 0
+        and 32 <= nMp <= 320
+        and 0 <= nMp - W.shape[1] < 32
+        and table.is_contiguous()
+        and hip_ext() is not None
+    )
+
+
+def _static_vectors_fused(table: torch.Tensor, W: torch.Tensor) -> bool:
+    mode = os.environ.get("SRX_STATIC_VECTORS", "")
+    if mode not in ("", "fused", "composed"):
+        raise ValueError(
+            f"SRX_STATIC_VECTORS={mode!r}: expected 'fused' or 'composed'")
+    if mode == "composed" or not W.is_cuda:
+        return False
+    _want_hip(W)  # a GPU run without the extension is an error, as elsewhere
+    if not static_vectors_available(table, W):
+        return False
+    return mode == "fused" or STATIC_VECTORS_FUSED_DEFAULT
+
+
+def _rows_i32(rows: torch.Tensor) -> torch.Tensor:
+    return rows if rows.dtype == torch.int32 else rows.int()
+
+
+class _StaticVectors(torch.autograd.Function):
+    """Y [T, nO] = table[rows] @ W^T, zero rows for rows < 0.  The table is
+    data: backward returns dW only."""
+
+    @staticmethod
+    def forward(ctx, W, table, rows):
+        ctx.fused = _static_vectors_fused(table, W)
+        if ctx.fused:
+            rows = _rows_i32(rows).contiguous()
+            Y = W.new_empty(rows.shape[0], W.shape[0])
+            hip_ext().static_vectors_fwd(table, rows, W.contiguous(), Y, 0)
+        else:
+            Y = ref.static_vectors_forward(table, rows, W)
+        ctx.save_for_backward(table, rows)
+        ctx.shape = tuple(W.shape)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        table, rows = ctx.saved_tensors
+        nO, nM = ctx.shape
+        if ctx.fused:
+            if dY.stride(1) != 1:
+                dY = dY.contiguous()
+            dW = hip_ext().static_vectors_bwd_dw(table, rows, dY, 0, nO,
+                                                 0, nM).to(dY.dtype)
+        else:
+            dW = ref.static_vectors_backward(dY, table, rows, nM)
+        return dW, None, None
+
+
+def static_vectors(W: torch.Tensor, table: torch.Tensor,
+                   rows: torch.Tensor) -> torch.Tensor:
+    return _StaticVectors.apply(W, table, rows)
+
+
+class _MultiHashEmbedVectors(torch.autograd.Function):
+    """_MultiHashEmbed with the static-vectors projection as one more (the
+    LAST) column block of the same [T, (n+1) W] matrix: the fused forward
+    writes its block in place, the backward reads dX's strided block."""
+
+    @staticmethod
+    def forward(ctx, ids4, seeds, vtable, vrows, vW, *tables):
+        hip = hip_ext()
+        T = ids4.shape[0]
+        W = tables[0].shape[1]
+        n = len(tables)
+        X = tables[0].new_empty(T, W * (n + 1))
+        rows_all = []
+        for i, table in enumerate(tables):
+            _, rows = hip.hashembed_fwd(table, ids4[:, i].contiguous(),
+                                        int(seeds[i]), X, i * W)
+            rows_all.append(rows)
+        ctx.fused = _static_vectors_fused(vtable, vW)
+        if ctx.fused:
+            vrows = _rows_i32(vrows).contiguous()
+            hip.static_vectors_fwd(vtable, vrows, vW.contiguous(), X, n * W)
+        else:
+            X[:, n * W:] = ref.static_vectors_forward(vtable, vrows, vW)
+        ctx.save_for_backward(vtable, vrows, *rows_all)
+        ctx.nrows = [t.shape[0] for t in tables]
+        ctx.W = W
+        ctx.vshape = tuple(vW.shape)
+        return X
+
+    @staticmethod
+    def backward(ctx, dX):
+        hip = hip_ext()
+        vtable, vrows, *rows_all = ctx.saved_tensors
+        W = ctx.W
+        n = len(rows_all)
+        det = deterministic()
+        grads = []
+        for i, rows in enumerate(rows_all):
+            dY = dX[:, i * W : (i + 1) * W]  # strided view, no copy
+            dst = rows.reshape(-1)
+            order = torch.argsort(dst, stable=True) if det else torch.argsort(dst)
+            dst_sorted = dst[order].contiguous().int()
+            src = (order // 4).int()
+            acc_dt = torch.int64 if det else torch.float32
+            dT32 = torch.zeros(ctx.nrows[i], W, dtype=acc_dt, device=dX.device)
+            hip.seg_scatter_add(dst_sorted, src, dY, dT32)
+            if det:
+                dT32 = dT32.to(torch.float32) / FIXED_SCALE
+            grads.append(dT32.to(dX.dtype))
+        nO, nM = ctx.vshape
+        if ctx.fused:
+            if dX.stride(1) != 1:
+                dX = dX.contiguous()
+            dvW = hip.static_vectors_bwd_dw(vtable, vrows, dX, n * W, nO,
+                                            0, nM).to(dX.dtype)
+        else:
+            dvW = ref.static_vectors_backward(dX[:, n * W:], vtable, vrows, nM)
+        return (None, None, None, None, dvW, *grads)
+
+
+def multi_hashembed_vectors(ids4: torch.Tensor, seeds, tables,
+                            vtable: torch.Tensor, vrows: torch.Tensor,
+                            vW: torch.Tensor) -> torch.Tensor:
+    """multi_hashembed plus the static-vectors block (last columns)."""
+    if ids4.is_cuda and _want_hip(tables[0]) and vW.shape[0] == tables[0].shape[1]:
+        return _MultiHashEmbedVectors.apply(ids4, list(seeds), vtable, vrows,
+                                            vW, *tables)
+    return torch.cat([multi_hashembed(ids4, seeds, tables),
+                      static_vectors(vW, vtable, vrows)], dim=1)
 
 
 # ------------------------------------------------------------- layernorm

@@ -15,6 +15,7 @@
 #include "srx_embed_parser.hip.h"
 #include "srx_softmax_reduce.hip.h"
 #include "srx_mwe.hip.h"
+#include "srx_staticvec.hip.h"
 #include "srx_activations.hip.h"
 #include "srx_attn.hip.h"
 
@@ -1262,6 +1263,143 @@ std::vector<at::Tensor> mwe_bwd_fused(at::Tensor dY,
           sums.narrow(0, 2L * W, 3L * W)};
 }
 
+// ------------------------------------------------- static word vectors
+// see srx_staticvec.hip.h.  `rows` must be < V: vocab.Vectors.find_rows
+// guarantees it on the host where the rows are built (no device sync here);
+// the kernels treat anything else as out of vocabulary.
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+void check_static_vectors(const at::Tensor& table, const at::Tensor& rows,
+                          int nO, int nM) {
+  check_dev(table);
+  check_dev(rows);
+  TORCH_CHECK(table.scalar_type() == at::kBFloat16 && table.dim() == 2,
+              "static_vectors: table must be bf16 [V, nMp]");
+  TORCH_CHECK(rows.scalar_type() == at::kInt && rows.dim() == 1,
+              "static_vectors: rows must be int32 [T]");
+  const long nMp = table.size(1);
+  TORCH_CHECK(nMp % 32 == 0 && nMp >= 32 && nMp <= 320,
+              "static_vectors: table row stride must be a multiple of 32, <= 320");
+  TORCH_CHECK(nM <= nMp && nMp - nM < 32,
+              "static_vectors: table stride must be roundup(nM, 32)");
+  TORCH_CHECK(nO == 96 || nO == 128, "static_vectors supports nO in {96,128}");
+  TORCH_CHECK(table.size(0) < (1L << 31), "static_vectors: too many rows");
+}
+
+template <int NO>
+void launch_static_vectors_fwd(const at::Tensor& table, const at::Tensor& rows,
+                               const at::Tensor& W, at::Tensor& Y, int col_off,
+                               hipStream_t stream) {
+  using C = SvCfg<NO>;
+  const long T = rows.size(0);
+  const int nMp = (int)table.size(1), nM = (int)W.size(1);
+  auto lds_for = [](int k) {
+    size_t img = (size_t)(C::MT * (k + 8) + C::B_ELEMS) * sizeof(bf16_t) +
+                 C::MT * sizeof(int);
+    return std::max(img, (size_t)C::MT * C::YP * sizeof(bf16_t));
+  };
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)static_vectors_fwd_kernel<NO>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_for(C::MAXK));
+    attr_set = true;
+  }
+  const long ldY = Y.stride(0);
+  const int w_vec = (nM % 8 == 0) && aligned16(W.data_ptr());
+  bf16_t* yp = (bf16_t*)Y.data_ptr();
+  const int y_vec = (ldY % 8 == 0) && (col_off % 8 == 0) && aligned16(yp);
+  dim3 grid((unsigned)((T + C::MT - 1) / C::MT));
+  hipLaunchKernelGGL((static_vectors_fwd_kernel<NO>), grid, dim3(C::NT),
+                     lds_for(nMp), stream, (const bf16_t*)table.data_ptr(),
+                     rows.data_ptr<int>(), (const bf16_t*)W.data_ptr(), yp, ldY,
+                     col_off, T, (int)table.size(0), nM, nMp, w_vec, y_vec);
+}
+
+void static_vectors_fwd(at::Tensor table, at::Tensor rows, at::Tensor W,
+                        at::Tensor Y, int64_t col_off) {
+  check_dev(W);
+  TORCH_CHECK(W.scalar_type() == at::kBFloat16 && W.dim() == 2,
+              "static_vectors_fwd: W must be bf16 [nO, nM]");
+  const int nO = (int)W.size(0);
+  check_static_vectors(table, rows, nO, (int)W.size(1));
+  const long T = rows.size(0);
+  TORCH_CHECK(Y.is_cuda() && Y.scalar_type() == at::kBFloat16 && Y.dim() == 2 &&
+                  Y.stride(1) == 1,
+              "static_vectors_fwd: Y must be a bf16 matrix with unit column stride");
+  TORCH_CHECK(Y.size(0) >= T && col_off >= 0 && col_off + nO <= Y.size(1) &&
+                  Y.stride(0) >= Y.size(1),
+              "static_vectors_fwd: column block outside Y");
+  if (T == 0) return;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  if (nO == 96)
+    launch_static_vectors_fwd<96>(table, rows, W, Y, (int)col_off, stream);
+  else
+    launch_static_vectors_fwd<128>(table, rows, W, Y, (int)col_off, stream);
+}
+
+template <int NO>
+void launch_static_vectors_bwd(const at::Tensor& table, const at::Tensor& rows,
+                               const at::Tensor& dX, int col_off, at::Tensor& ws,
+                               int G, int ntiles, hipStream_t stream) {
+  using C = SvCfg<NO>;
+  const int nMp = (int)table.size(1);
+  auto lds_for = [](int k) {
+    return (size_t)(NO + k) * C::TP * sizeof(bf16_t) + C::MT * sizeof(int);
+  };
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)static_vectors_bwd_dw_kernel<NO>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_for(C::MAXK));
+    attr_set = true;
+  }
+  const long ldX = dX.stride(0);
+  const bf16_t* xp = (const bf16_t*)dX.data_ptr();
+  const int x_vec = (ldX % 8 == 0) && (col_off % 8 == 0) && aligned16(xp);
+  hipLaunchKernelGGL((static_vectors_bwd_dw_kernel<NO>), dim3((unsigned)G),
+                     dim3(C::NT), lds_for(nMp), stream,
+                     (const bf16_t*)table.data_ptr(), rows.data_ptr<int>(), xp, ldX,
+                     col_off, ws.data_ptr<float>(), (long)rows.size(0),
+                     (int)table.size(0), nMp, ntiles, x_vec);
+}
+
+at::Tensor static_vectors_bwd_dw(at::Tensor table, at::Tensor rows, at::Tensor dX,
+                                 int64_t col_off, int64_t nO,
+                                 int64_t max_groups, int64_t nM) {
+  if (nM <= 0) nM = table.size(1);
+  check_static_vectors(table, rows, (int)nO, (int)nM);
+  const long T = rows.size(0);
+  TORCH_CHECK(dX.is_cuda() && dX.scalar_type() == at::kBFloat16 && dX.dim() == 2 &&
+                  dX.stride(1) == 1,
+              "static_vectors_bwd_dw: dX must be a bf16 matrix with unit column stride");
+  TORCH_CHECK(dX.size(0) >= T && col_off >= 0 && col_off + nO <= dX.size(1) &&
+                  dX.stride(0) >= dX.size(1),
+              "static_vectors_bwd_dw: column block outside dX");
+  auto f32 = table.options().dtype(at::kFloat);
+  if (T == 0) return at::zeros({nO, nM}, f32);
+  const long ntiles = (T + 127) / 128;
+  // one workgroup per CU (122 KB of LDS at nMp = 320)
+  long G = std::min<long>(ntiles,
+                          at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
+  if (max_groups > 0) G = std::min<long>(G, max_groups);
+  const long nMp = table.size(1);
+  auto ws = at::empty({G, nO, nMp}, f32);
+  auto dW = at::empty({nO, nM}, f32);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  if (nO == 96)
+    launch_static_vectors_bwd<96>(table, rows, dX, (int)col_off, ws, (int)G,
+                                  (int)ntiles, stream);
+  else
+    launch_static_vectors_bwd<128>(table, rows, dX, (int)col_off, ws, (int)G,
+                                   (int)ntiles, stream);
+  const int total = (int)(nO * nM);
+  hipLaunchKernelGGL(static_vectors_reduce_kernel, dim3((total + kBlock - 1) / kBlock),
+                     dim3(kBlock), 0, stream, ws.data_ptr<float>(),
+                     dW.data_ptr<float>(), (int)G, (int)nO, (int)nM, (int)nMp);
+  return dW;
+}
+
 // --------------------------------------------- fused transition step (C++)
 // One python call per transition step: state scorer kernel + upper GEMM +
 // on-device action selection, with a C++ autograd node so the per-step
@@ -1406,6 +1544,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mwe_bwd_fused", &mwe_bwd_fused, py::arg("dY"), py::arg("dropmask"),
         py::arg("Mout"), py::arg("g"), py::arg("mu"), py::arg("rstd"),
         py::arg("which"), py::arg("weight"), py::arg("starts"), py::arg("ends"));
+  m.def("static_vectors_fwd", &static_vectors_fwd, py::arg("table"),
+        py::arg("rows"), py::arg("W"), py::arg("Y"), py::arg("col_off") = 0);
+  m.def("static_vectors_bwd_dw", &static_vectors_bwd_dw, py::arg("table"),
+        py::arg("rows"), py::arg("dX"), py::arg("col_off"), py::arg("nO"),
+        py::arg("max_groups") = 0, py::arg("nM") = 0);
   m.def("fused_step", &fusedstep::fused_step);
   m.def("fused_entries_take", &fusedstep::fused_entries_take);
   m.def("transition_ce", &transition_ce, py::arg("scores"), py::arg("gold"),

@@ -89,6 +89,29 @@ def hashembed_backward(dY: torch.Tensor, rows: torch.Tensor, nrows: int) -> torc
     return dT
 
 
+def static_vectors_gather(table: torch.Tensor, rows: torch.Tensor, nM: int) -> torch.Tensor:
+    """table[rows][:, :nM] with out-of-vocabulary rows (rows < 0) ZEROED
+    AFTER the gather (the index is only made valid, never trusted)."""
+    oov = rows < 0
+    G = table.index_select(0, rows.long().clamp_(min=0))[:, :nM]
+    return G.masked_fill(oov[:, None], 0)
+
+
+def static_vectors_forward(table: torch.Tensor, rows: torch.Tensor,
+                           W: torch.Tensor) -> torch.Tensor:
+    """table [V, >= nM], rows [T] int (-1 = OOV), W [nO, nM] -> [T, nO] =
+    table[rows] @ W^T, zero for OOV rows (spaCy StaticVectors contract)."""
+    return static_vectors_gather(table, rows, W.shape[1]).to(W.dtype).mm(W.t())
+
+
+def static_vectors_backward(dY: torch.Tensor, table: torch.Tensor,
+                            rows: torch.Tensor, nM: int) -> torch.Tensor:
+    """dW [nO, nM] = dY^T @ table[rows]; OOV rows contribute nothing.  No
+    gradient flows to the table or the rows."""
+    G = static_vectors_gather(table, rows, nM).to(dY.dtype)
+    return dY.masked_fill((rows < 0)[:, None], 0).t().mm(G)
+
+
 def layernorm(X: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float = 1e-5):
     mu = X.mean(dim=-1, keepdim=True)
     var = X.var(dim=-1, unbiased=False, keepdim=True)

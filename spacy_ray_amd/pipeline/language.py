@@ -266,6 +266,9 @@ class Language:
         vocab_dir = path / "vocab"
         vocab_dir.mkdir(exist_ok=True)
         (vocab_dir / "strings.json").write_text(json.dumps(self.vocab.strings.to_list()))
+        if self.vocab.vectors is not None:
+            # vectors.safetensors + vectors.json, only when a table is loaded
+            self.vocab.vectors.to_disk(vocab_dir)
         # tokenizer settings file (spaCy layout has a `tokenizer` blob)
         from spacy_ray_amd.vocab.tokenizer import tokenizer_to_bytes
 
@@ -297,10 +300,18 @@ class Language:
         strings = json.loads((path / "vocab" / "strings.json").read_text())
         for s in strings:
             self.vocab.strings.add(s)
+        from spacy_ray_amd.models.architectures import building_for
+        from spacy_ray_amd.vocab.vectors import Vectors
+
+        # before the pipes: a StaticVectors layer sizes itself from the table
+        vectors = Vectors.from_disk(path / "vocab")
+        if vectors is not None:
+            self.vocab.vectors = vectors
         for name, pipe in self.pipeline:
             pdir = path / name
             if (pdir / "cfg.json").exists():
-                pipe.load_cfg(json.loads((pdir / "cfg.json").read_text()), self.device)
+                with building_for(self.vocab):
+                    pipe.load_cfg(json.loads((pdir / "cfg.json").read_text()), self.device)
             mfile = pdir / "model.safetensors"
             if mfile.exists() and pipe.module is not None:
                 from safetensors.torch import load_file
@@ -403,6 +414,7 @@ def init_nlp(config: Config, device: str = "cpu", sample_size: int = 128) -> Lan
     seed = int(cfg.get("training", {}).get("seed", 0) or 0)
     torch.manual_seed(seed)
     nlp = build_nlp(config, device=device)
+    load_init_vectors(nlp, cfg)
     (train_corpus,) = resolve_dot_names(cfg, [cfg["training"]["train_corpus"]])
     if "transformer" in nlp.pipe_names:
         # the transformer trains its byte-level BPE on this sample at init;
@@ -433,6 +445,71 @@ def init_nlp(config: Config, device: str = "cpu", sample_size: int = 128) -> Lan
         if label_sets[name]:
             pipe.labels = sorted(label_sets[name])
         pipe.label2id = {t: i for i, t in enumerate(pipe.labels)}
-    for name, pipe in nlp.pipeline:
-        pipe.initialize(sample, nlp.device)
+    from spacy_ray_amd.models.architectures import building_for
+
+    with building_for(nlp.vocab):
+        for name, pipe in nlp.pipeline:
+            pipe.initialize(sample, nlp.device)
     return nlp
+
+
+def load_init_vectors(nlp: Language, cfg: Dict) -> None:
+    """[initialize] vectors = <pipeline dir written by `init vectors`>:
+    load that directory's table into nlp.vocab (no-op when unset)."""
+    path = (cfg.get("initialize") or {}).get("vectors")
+    if not path:
+        return
+    from spacy_ray_amd.vocab.vectors import load_vectors_dir
+
+    nlp.vocab.vectors = load_vectors_dir(path)
+
+
+def init_vectors(lang: str, vectors_loc, output_dir, *, truncate: int = 0,
+                 name: Optional[str] = None) -> Language:
+    """word2vec text file -> a pipeline directory with an empty pipeline
+    and a vocab that holds the vectors (`spacy-mi init vectors`)."""
+    from spacy_ray_amd.vocab.vectors import Vectors, read_word2vec_text
+
+    words, data = read_word2vec_text(vectors_loc, truncate=truncate)
+    config = Config.from_str(f'[nlp]\nlang = "{lang}"\npipeline = []\n')
+    nlp = build_nlp(config)
+    nlp.vocab.vectors = Vectors.from_words(words, data,
+                                           name=name or f"{lang}_vectors")
+    for w in words:
+        nlp.vocab.strings.add(w)
+    nlp.to_disk(output_dir)
+    return nlp
+
+
+def _wants_static_vectors(node) -> bool:
+    if isinstance(node, dict):
+        arch = node.get("@architectures", "")
+        if arch == "spacy.MultiHashEmbed.v2" and node.get("include_static_vectors"):
+            return True
+        if arch == "spacy.HashEmbedCNN.v2" and node.get("pretrained_vectors"):
+            return True
+        return any(_wants_static_vectors(v) for v in node.values())
+    return False
+
+
+def check_static_vectors_config(cfg: Dict) -> List[str]:
+    """`debug config`: include_static_vectors and [initialize] vectors must
+    come as a pair, and the directory must hold a table.  Returns report
+    lines; raises ValueError on a broken pair."""
+    wants = _wants_static_vectors(cfg.get("components", {}))
+    path = (cfg.get("initialize") or {}).get("vectors")
+    if wants and not path:
+        raise ValueError(
+            "include_static_vectors = true but [initialize] vectors is not "
+            "set: point it (or [paths] vectors) at a directory written by "
+            "`spacy-mi init vectors`")
+    if not path:
+        return []
+    from spacy_ray_amd.vocab.vectors import load_vectors_dir
+
+    vectors = load_vectors_dir(path)
+    lines = [f"vectors OK: {vectors!r}"]
+    if not wants:
+        lines.append("note: [initialize] vectors is set but no model has "
+                     "include_static_vectors = true (Doc.vector only)")
+    return lines

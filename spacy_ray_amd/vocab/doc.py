@@ -24,16 +24,40 @@ class Vocab:
     def __init__(self, lang: str = "xx") -> None:
         self.lang = lang
         self.strings = StringStore()
+        # static word vectors (vocab/vectors.py); None = no table loaded
+        self.vectors = None
+        # key attrs of the StaticVectors layers built against this vocab:
+        # TokenBatch ships vector rows only for these
+        self.vector_key_attrs: List[str] = []
 
     def __repr__(self) -> str:
         return f"Vocab(lang={self.lang!r}, strings={len(self.strings)})"
+
+    def _vector_row(self, word: str) -> int:
+        if self.vectors is None:
+            return -1
+        key = word.lower() if self.vectors.key_attr != "ORTH" else word
+        return int(self.vectors.find_words([key])[0])
+
+    def has_vector(self, word: str) -> bool:
+        return self._vector_row(word) >= 0
+
+    def get_vector(self, word: str) -> np.ndarray:
+        """The word's vector under the table's key attribute; zeros when it
+        is out of vocabulary or no vectors are loaded."""
+        if self.vectors is None:
+            return np.zeros(0, dtype=np.float32)
+        row = self._vector_row(word)
+        if row < 0:
+            return np.zeros(self.vectors.width, dtype=np.float32)
+        return self.vectors.data[row].copy()
 
 
 class Doc:
     __slots__ = (
         "vocab", "words", "spaces", "attr_hashes",
         "tags", "heads", "deps", "ents", "sent_starts", "cats", "morphs",
-        "lemmas", "spans", "tensor", "user_data",
+        "lemmas", "spans", "tensor", "user_data", "vector_rows",
     )
 
     def __init__(
@@ -75,9 +99,48 @@ class Doc:
         self.lemmas = list(lemmas) if lemmas is not None else None
         self.tensor: Optional[np.ndarray] = None
         self.user_data: Dict = {}
+        # key_attr -> (Vectors, int32 rows [n]); filled lazily by
+        # get_vector_rows and shared with copy_unannotated, like attr_hashes
+        self.vector_rows: Dict[str, tuple] = {}
 
     def __len__(self) -> int:
         return len(self.words)
+
+    def get_vector_rows(self, key_attr: Optional[str] = None) -> np.ndarray:
+        """Rows of this doc's tokens in vocab.vectors (-1 = OOV).  "ORTH"
+        hashes the token text; "LOWER" / "NORM" reuse attr_hashes[:, 0]."""
+        vectors = self.vocab.vectors
+        if vectors is None:
+            raise ValueError("the vocab has no vectors loaded")
+        key_attr = key_attr or vectors.key_attr
+        cached = self.vector_rows.get(key_attr)
+        if cached is not None and cached[0] is vectors:
+            return cached[1]
+        if key_attr == "ORTH":
+            rows = vectors.find_words(self.words)
+        elif key_attr in ("LOWER", "NORM"):
+            rows = vectors.find_rows(self.attr_hashes[:, 0])
+        else:
+            raise ValueError(f"unsupported vectors key_attr {key_attr!r}")
+        self.vector_rows[key_attr] = (vectors, rows)
+        return rows
+
+    @property
+    def vector(self) -> np.ndarray:
+        """Mean of the in-vocabulary token vectors, or zeros."""
+        vectors = self.vocab.vectors
+        if vectors is None:
+            return np.zeros(0, dtype=np.float32)
+        rows = self.get_vector_rows()
+        rows = rows[rows >= 0]
+        if not len(rows):
+            return np.zeros(vectors.width, dtype=np.float32)
+        return vectors.data[rows].mean(axis=0)
+
+    def similarity(self, other: "Doc") -> float:
+        from .vectors import cosine
+
+        return cosine(self.vector, other.vector)
 
     def __iter__(self) -> Iterator[str]:
         return iter(self.words)
@@ -95,8 +158,10 @@ class Doc:
         # words are identical, so the (n,4) attr-hash array is shared (it is
         # never mutated) — re-hashing every token per epoch/predict call was
         # pure waste on the Example.from_doc path
-        return Doc(self.vocab, self.words, spaces=self.spaces,
-                   attr_hashes=self.attr_hashes)
+        doc = Doc(self.vocab, self.words, spaces=self.spaces,
+                  attr_hashes=self.attr_hashes)
+        doc.vector_rows = self.vector_rows
+        return doc
 
     def to_dict(self) -> Dict:
         return {

@@ -207,8 +207,71 @@ def bench_attn():
     timeit("attn sdpa  fwd+bwd (1k win)", sdpa_fb)
 
 
+def timeit_events(name, fn, iters=30, warmup=10):
+    """Median and min of per-call GPU times (hip events around each call,
+    after a warm-up that also settles the clocks)."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(iters):
+        a = torch.cuda.Event(enable_timing=True)
+        b = torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    times.sort()
+    med = times[len(times) // 2]
+    print(f"{name:40s} median {med:8.3f} ms  min {times[0]:8.3f} ms")
+    return med
+
+
+def bench_static_vectors():
+    """static_vectors_fwd / static_vectors_bwd_dw against the composed path
+    (index_select + mm, dY^T @ gathered) on the same inputs: T = 1M tokens,
+    V = 20000, nM = 300 (table stride 320), Zipf-distributed rows with 5%
+    out of vocabulary.  Both write / read the last column block of a
+    [T, 5 nO] embed matrix, as MultiHashEmbed does."""
+    import numpy as np
+
+    T, V, nM, nMp = 1 << 20, 20000, 300, 320
+    rng = np.random.default_rng(0)
+    p = 1.0 / np.arange(1, V + 1)
+    rows_np = rng.choice(V, size=T, p=p / p.sum()).astype(np.int32)
+    rows_np[rng.random(T) < 0.05] = -1
+    rows = torch.from_numpy(rows_np).to(dev)
+    table = torch.zeros(V, nMp, device=dev, dtype=torch.bfloat16)
+    table[:, :nM] = torch.randn(V, nM, device=dev) * 0.5
+    oov = (rows < 0)[:, None]
+    idx = rows.long().clamp(min=0)
+    for nO in (96, 128):
+        W = (torch.randn(nO, nM, device=dev) / nM ** 0.5).to(torch.bfloat16)
+        X = torch.zeros(T, 5 * nO, device=dev, dtype=torch.bfloat16)
+        dX = (torch.randn(T, 5 * nO, device=dev) * 0.1).to(torch.bfloat16)
+
+        def composed_fwd():
+            G = table.index_select(0, idx)[:, :nM].masked_fill(oov, 0)
+            X[:, 4 * nO:] = G.mm(W.t())
+
+        def composed_dw():
+            G = table.index_select(0, idx)[:, :nM].masked_fill(oov, 0)
+            return dX[:, 4 * nO:].t().mm(G)
+
+        tag = f"(T=1M,nM=300,nO={nO})"
+        timeit_events(f"static_vectors_fwd {tag}",
+                      lambda: hip.static_vectors_fwd(table, rows, W, X, 4 * nO))
+        timeit_events(f"composed fwd {tag}", composed_fwd)
+        timeit_events(f"static_vectors_bwd_dw {tag}",
+                      lambda: hip.static_vectors_bwd_dw(table, rows, dX, 4 * nO,
+                                                        nO, 0, nM))
+        timeit_events(f"composed dW {tag}", composed_dw)
+
+
 ALL = {"mwe": bench_mwe, "dpre": bench_dpre, "ce": bench_ce,
-       "gpustate": bench_gpustate, "attn": bench_attn}
+       "gpustate": bench_gpustate, "attn": bench_attn,
+       "static_vectors": bench_static_vectors}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(ALL)
