@@ -123,6 +123,104 @@ def maxout(X: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------- hashembed
+def _hashembed_legacy() -> bool:
+    """SRX_HASHEMBED=legacy: the per-table forward launches and the
+    per-destination (4T-entry) sorted backward, for comparison and as an
+    escape hatch."""
+    mode = os.environ.get("SRX_HASHEMBED", "")
+    if mode not in ("", "legacy"):
+        raise ValueError(f"SRX_HASHEMBED={mode!r}: expected 'legacy' or unset")
+    return mode == "legacy"
+
+
+def _multi_fwd_ok(ids4: torch.Tensor, tables) -> bool:
+    """multi_hashembed_fwd's fast path: equal W across tables, W % 8 == 0,
+    bf16 or fp32; anything else takes the per-table launches."""
+    t0 = tables[0]
+    W = t0.shape[1]
+    n = len(tables)
+    vec = 8 if t0.dtype == torch.bfloat16 else 4
+    return (
+        not _hashembed_legacy()
+        and 1 <= n <= 8
+        and W % 8 == 0
+        and t0.dtype in (torch.bfloat16, torch.float32)
+        and all(t.dim() == 2 and t.shape[1] == W and t.dtype == t0.dtype
+                and t.is_contiguous() and t.shape[0] >= 1 for t in tables)
+        and ids4.dtype == torch.int64
+        and (ids4.stride(1) == 1 or ids4.shape[1] == 1)
+        and ids4.shape[0] * n * (W // vec) < 2 ** 31
+    )
+
+
+def _multi_hashembed_fwd(ids4: torch.Tensor, seeds, tables, X: torch.Tensor):
+    """Write the n tables' column blocks [0, n W) of X.  Returns (rows, keys):
+    per-table [T, 4] int32 rows, and the per-table int32 sort keys of the
+    merged backward (None on the per-table path)."""
+    hip = hip_ext()
+    if _multi_fwd_ok(ids4, tables):
+        rows, keys = hip.multi_hashembed_fwd(
+            ids4, list(tables), [int(s) for s in seeds], X, 0)
+        return list(rows.unbind(0)), list(keys.unbind(0))
+    W = tables[0].shape[1]
+    rows_all = []
+    for i, table in enumerate(tables):
+        _, rows = hip.hashembed_fwd(table, ids4[:, i].contiguous(),
+                                    int(seeds[i]), X, i * W)
+        rows_all.append(rows)
+    return rows_all, None
+
+
+def _hashembed_sort_key(rows: torch.Tensor, nrows: int) -> torch.Tensor:
+    """The forward kernel's sort key, for callers that took the per-table
+    forward (mirrors hashembed_sort_key in srx_embed_parser.hip.h)."""
+    if nrows * nrows < 2 ** 31:
+        return rows[:, 0] * nrows + rows[:, 1]
+    return rows[:, 0].contiguous()
+
+
+def _hashembed_table_grad(dY: torch.Tensor, rows: torch.Tensor,
+                          key: Optional[torch.Tensor], nrows: int) -> torch.Tensor:
+    """One table's gradient from dY (a row view, e.g. a column block of the
+    embed gradient).  Default: sort the T tokens by key, merge runs of equal
+    row quadruples (hashembed_bwd_merged).  Deterministic mode and
+    SRX_HASHEMBED=legacy: sort the 4T destinations (stable in deterministic
+    mode) and seg_scatter_add, into an int64 fixed-point sink when
+    deterministic."""
+    hip = hip_ext()
+    det = deterministic()
+    W = dY.shape[1]
+    if det or _hashembed_legacy():
+        dst = rows.reshape(-1)
+        order = torch.argsort(dst, stable=True) if det else torch.argsort(dst)
+        dst_sorted = dst[order].contiguous().int()
+        src = (order // 4).int()
+        acc_dt = torch.int64 if det else torch.float32
+        dT32 = torch.zeros(nrows, W, dtype=acc_dt, device=dY.device)
+        hip.seg_scatter_add(dst_sorted, src, dY, dT32)
+        if det:
+            dT32 = dT32.to(torch.float32) / FIXED_SCALE
+        return dT32.to(dY.dtype)
+    if key is None:
+        key = _hashembed_sort_key(rows, nrows)
+    order = torch.argsort(key)
+    dT32 = torch.zeros(nrows, W, dtype=torch.float32, device=dY.device)
+    hip.hashembed_bwd_merged(order, rows, dY, dT32)
+    return dT32.to(dY.dtype)
+
+
+def _hashembed_table_grads(dX: torch.Tensor, rows_all, keys_all, nrows, W: int):
+    """Per-table gradients from the column blocks of dX (strided views, no
+    copies)."""
+    if dX.stride(1) != 1:
+        dX = dX.contiguous()
+    return [
+        _hashembed_table_grad(dX[:, i * W:(i + 1) * W], rows,
+                              keys_all[i] if keys_all else None, nrows[i])
+        for i, rows in enumerate(rows_all)
+    ]
+
+
 class _HashEmbed(torch.autograd.Function):
     """table [R, W], ids [T] int64(bit-cast uint64), seed -> [T, W].
 
@@ -132,41 +230,37 @@ class _HashEmbed(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table: torch.Tensor, ids: torch.Tensor, seed: int) -> torch.Tensor:
         nrows = table.shape[0]
+        key = None
         if _want_hip(table):
-            Y, rows = hip_ext().hashembed_fwd(table, ids.contiguous(), seed)
+            ids = ids.contiguous()
+            if _multi_fwd_ok(ids.view(-1, 1), [table]):
+                Y = table.new_empty(ids.shape[0], table.shape[1])
+                rows, key = (t[0] for t in hip_ext().multi_hashembed_fwd(
+                    ids.view(-1, 1), [table], [int(seed)], Y, 0))
+            else:
+                Y, rows = hip_ext().hashembed_fwd(table, ids, seed)
         else:
             rows_np = ref.hashembed_rows_cpu(
                 ids.cpu().numpy().view("uint64"), seed, nrows
             )
             rows = torch.from_numpy(rows_np).to(ids.device)
             Y = ref.hashembed_forward(table, rows)
-        ctx.save_for_backward(rows)
+        ctx.save_for_backward(rows, *([] if key is None else [key]))
         ctx.nrows = nrows
         return Y
 
     @staticmethod
     def backward(ctx, dY: torch.Tensor):
-        (rows,) = ctx.saved_tensors
+        rows, *key = ctx.saved_tensors
         if _want_hip(dY):
             hip = hip_ext()
             T = dY.shape[0]
-            det = deterministic()
-            if T >= 4096 or det:
+            if T >= 4096 or deterministic():
                 # Zipf-hot rows serialize plain atomics (1.5 ms/call at
-                # T=128k measured) — sort by destination row + chunked
-                # segmented reduction instead (SURVEY.md §7 hard-part 2).
-                # Deterministic mode: stable sort + int64 fixed-point sink.
-                dst = rows.reshape(-1)
-                order = torch.argsort(dst, stable=True) if det else torch.argsort(dst)
-                dst_sorted = dst[order].contiguous().int()
-                src = (order // 4).int()
-                acc_dt = torch.int64 if det else torch.float32
-                dT32 = torch.zeros(ctx.nrows, dY.shape[1], dtype=acc_dt,
-                                   device=dY.device)
-                hip.seg_scatter_add(dst_sorted, src, dY.contiguous(), dT32)
-                if det:
-                    dT32 = dT32.to(torch.float32) / FIXED_SCALE
-                dT = dT32.to(dY.dtype)
+                # T=128k measured) — sort + segmented reduction instead
+                # (SURVEY.md §7 hard-part 2).
+                dT = _hashembed_table_grad(dY.contiguous(), rows,
+                                           key[0] if key else None, ctx.nrows)
             else:
                 dT = hip.hashembed_bwd(dY.contiguous(), rows, ctx.nrows)
         else:
@@ -180,46 +274,28 @@ def hashembed(table: torch.Tensor, ids: torch.Tensor, seed: int) -> torch.Tensor
 
 class _MultiHashEmbed(torch.autograd.Function):
     """All 4 attr tables in one autograd node producing the concatenated
-    [T, 4W] matrix: forward writes each table's output straight into its
-    column block (no torch.cat — a 0.77 GB copy per step at 1M words);
-    backward runs the sorted segmented reduction per table on COLUMN VIEWS
-    of dX (strided seg_scatter source — no .contiguous() copies)."""
+    [T, 4W] matrix: one launch writes every table's column block (no
+    torch.cat — a 0.77 GB copy per step at 1M words) and the backward's
+    sort keys; backward runs the token-sorted merged reduction per table on
+    COLUMN VIEWS of dX (strided source — no .contiguous() copies)."""
 
     @staticmethod
     def forward(ctx, ids4, seeds, *tables):
-        hip = hip_ext()
         T = ids4.shape[0]
         W = tables[0].shape[1]
-        X = tables[0].new_empty(T, W * len(tables))
-        rows_all = []
-        for i, table in enumerate(tables):
-            _, rows = hip.hashembed_fwd(table, ids4[:, i].contiguous(),
-                                        int(seeds[i]), X, i * W)
-            rows_all.append(rows)
-        ctx.save_for_backward(*rows_all)
+        n = len(tables)
+        X = tables[0].new_empty(T, W * n)
+        rows_all, keys_all = _multi_hashembed_fwd(ids4, seeds, tables, X)
+        ctx.save_for_backward(*rows_all, *(keys_all or []))
         ctx.nrows = [t.shape[0] for t in tables]
         ctx.W = W
         return X
 
     @staticmethod
     def backward(ctx, dX):
-        hip = hip_ext()
-        rows_all = ctx.saved_tensors
-        W = ctx.W
-        det = deterministic()
-        grads = []
-        for i, rows in enumerate(rows_all):
-            dY = dX[:, i * W : (i + 1) * W]  # strided view, no copy
-            dst = rows.reshape(-1)
-            order = torch.argsort(dst, stable=True) if det else torch.argsort(dst)
-            dst_sorted = dst[order].contiguous().int()
-            src = (order // 4).int()
-            acc_dt = torch.int64 if det else torch.float32
-            dT32 = torch.zeros(ctx.nrows[i], W, dtype=acc_dt, device=dX.device)
-            hip.seg_scatter_add(dst_sorted, src, dY, dT32)
-            if det:
-                dT32 = dT32.to(torch.float32) / FIXED_SCALE
-            grads.append(dT32.to(dX.dtype))
+        n = len(ctx.nrows)
+        rows_all, keys_all = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
+        grads = _hashembed_table_grads(dX, rows_all, keys_all, ctx.nrows, ctx.W)
         return (None, None, *grads)
 
 
@@ -330,18 +406,14 @@ class _MultiHashEmbedVectors(torch.autograd.Function):
         W = tables[0].shape[1]
         n = len(tables)
         X = tables[0].new_empty(T, W * (n + 1))
-        rows_all = []
-        for i, table in enumerate(tables):
-            _, rows = hip.hashembed_fwd(table, ids4[:, i].contiguous(),
-                                        int(seeds[i]), X, i * W)
-            rows_all.append(rows)
+        rows_all, keys_all = _multi_hashembed_fwd(ids4, seeds, tables, X)
         ctx.fused = _static_vectors_fused(vtable, vW)
         if ctx.fused:
             vrows = _rows_i32(vrows).contiguous()
             hip.static_vectors_fwd(vtable, vrows, vW.contiguous(), X, n * W)
         else:
             X[:, n * W:] = ref.static_vectors_forward(vtable, vrows, vW)
-        ctx.save_for_backward(vtable, vrows, *rows_all)
+        ctx.save_for_backward(vtable, vrows, *rows_all, *(keys_all or []))
         ctx.nrows = [t.shape[0] for t in tables]
         ctx.W = W
         ctx.vshape = tuple(vW.shape)
@@ -350,23 +422,11 @@ class _MultiHashEmbedVectors(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dX):
         hip = hip_ext()
-        vtable, vrows, *rows_all = ctx.saved_tensors
+        vtable, vrows, *saved = ctx.saved_tensors
         W = ctx.W
-        n = len(rows_all)
-        det = deterministic()
-        grads = []
-        for i, rows in enumerate(rows_all):
-            dY = dX[:, i * W : (i + 1) * W]  # strided view, no copy
-            dst = rows.reshape(-1)
-            order = torch.argsort(dst, stable=True) if det else torch.argsort(dst)
-            dst_sorted = dst[order].contiguous().int()
-            src = (order // 4).int()
-            acc_dt = torch.int64 if det else torch.float32
-            dT32 = torch.zeros(ctx.nrows[i], W, dtype=acc_dt, device=dX.device)
-            hip.seg_scatter_add(dst_sorted, src, dY, dT32)
-            if det:
-                dT32 = dT32.to(torch.float32) / FIXED_SCALE
-            grads.append(dT32.to(dX.dtype))
+        n = len(ctx.nrows)
+        rows_all, keys_all = saved[:n], saved[n:]
+        grads = _hashembed_table_grads(dX, rows_all, keys_all, ctx.nrows, W)
         nO, nM = ctx.vshape
         if ctx.fused:
             if dX.stride(1) != 1:

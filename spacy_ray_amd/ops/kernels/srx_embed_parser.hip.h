@@ -71,6 +71,231 @@ __global__ void hashembed_bwd_kernel(const T* __restrict__ dY,
   }
 }
 
+// ------------------------------------------- multi-table hashembed fwd
+// All n attr tables of a MultiHashEmbed in ONE launch.  A thread handles one
+// 16-byte piece (V elements) of one table's output row: item = t * (n * LPT)
+// + i * LPT + p with LPT = W / V pieces per row, so consecutive lanes write
+// consecutive 16-byte pieces of the concatenated [T, ldX] row (768 B whole
+// rows at n = 4, W = 96 bf16) and every lane of a wave is busy.  Each lane
+// hashes ids[t, i] for its own table i (ids read in place, no column
+// copies); the lane with p == 0 also stores the row quadruple (one 16-byte
+// store) and the int32 sort key that hashembed_bwd_merged sorts by.
+// Per element the arithmetic is the per-table kernel's: ld(r0) + ld(r1) +
+// ld(r2) + ld(r3) in fp32, in that order, rounded once — bit-identical.
+// The caller guarantees nT * n * LPT < 2^31 (32-bit item arithmetic).
+#define SRX_MHE_MAX_TABLES 8
+
+struct MultiHashTables {
+  const void* table[SRX_MHE_MAX_TABLES];
+  uint32_t seed[SRX_MHE_MAX_TABLES];
+  int32_t nrows[SRX_MHE_MAX_TABLES];
+};
+
+// Sort key of a row quadruple: r0 * R + r1 where that fits an int32, else
+// r0.  Equal ids always get equal keys; the backward compares the whole
+// quadruple, so colliding keys cost adjacency only, never correctness.
+__device__ __forceinline__ int32_t hashembed_sort_key(int32_t r0, int32_t r1,
+                                                      int32_t nrows) {
+  return (long)nrows * nrows < 2147483648L ? r0 * nrows + r1 : r0;
+}
+
+template <typename T, int V>
+__global__ void multi_hashembed_fwd_kernel(MultiHashTables tabs,
+                                           const uint64_t* __restrict__ ids,
+                                           T* __restrict__ X,
+                                           int32_t* __restrict__ rows_out,
+                                           int32_t* __restrict__ keys_out,
+                                           long nT, int n, int W, long ldIds,
+                                           long ldX) {
+  const uint32_t LPT = (uint32_t)(W / V);
+  const uint32_t LP = (uint32_t)n * LPT;
+  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t tu = item / LP;
+  if ((long)tu >= nT) return;
+  const long t = tu;
+  const uint32_t j = item - tu * LP;
+  const int i = (int)(j / LPT);
+  const int p = (int)(j - (uint32_t)i * LPT);
+  // the by-value table descriptors live in scalar registers: pick this
+  // lane's with a select chain (a per-lane index would go through scratch)
+  const T* table = (const T*)tabs.table[0];
+  uint32_t seed = tabs.seed[0];
+  int32_t nrows = tabs.nrows[0];
+#pragma unroll
+  for (int k = 1; k < SRX_MHE_MAX_TABLES; k++) {
+    if (i == k) {
+      table = (const T*)tabs.table[k];
+      seed = tabs.seed[k];
+      nrows = tabs.nrows[k];
+    }
+  }
+  uint32_t h[4];
+  murmur3_hash4_u64_dev(ids[t * ldIds + i], seed, h);
+  const int32_t r0 = (int32_t)(h[0] % (uint32_t)nrows);
+  const int32_t r1 = (int32_t)(h[1] % (uint32_t)nrows);
+  const int32_t r2 = (int32_t)(h[2] % (uint32_t)nrows);
+  const int32_t r3 = (int32_t)(h[3] % (uint32_t)nrows);
+  if (p == 0) {
+    *(int4*)(rows_out + ((long)i * nT + t) * 4) = make_int4(r0, r1, r2, r3);
+    keys_out[(long)i * nT + t] = hashembed_sort_key(r0, r1, nrows);
+  }
+  float a[V], b[V], c[V], d[V], acc[V];
+  ElemV<T, V>::ld(table + (long)r0 * W + p * V, a);
+  ElemV<T, V>::ld(table + (long)r1 * W + p * V, b);
+  ElemV<T, V>::ld(table + (long)r2 * W + p * V, c);
+  ElemV<T, V>::ld(table + (long)r3 * W + p * V, d);
+#pragma unroll
+  for (int v = 0; v < V; v++) acc[v] = a[v] + b[v] + c[v] + d[v];
+  ElemV<T, V>::st(X + t * ldX + (long)i * W + p * V, acc);
+}
+
+// ---------------------------------- token-sorted, run-merged backward
+// dT32[rows[t, s]] += dY[t] for s in 0..3, over tokens in the order given by
+// `order` (tokens sorted by hashembed_sort_key).  The four rows of a token
+// are a function of its id alone, so every token of an id pushes the same
+// sum to the same four rows: a wave owns 128 consecutive sorted positions,
+// sums the dY rows of a run of EQUAL QUADRUPLES in fp32 registers and pushes
+// the sum to the run's four rows when the quadruple changes and at the
+// chunk's end.  Each dY row is read once (the per-destination path sorted 4T
+// entries and gathered every row four times).  A quadruple with repeated
+// rows pushes once per occurrence.
+//
+// Lane l loads order[] and the 16-byte quadruple of sorted positions l and
+// l + 64 of the chunk; entries are then broadcast with v_readlane (wave-
+// uniform index), and U dY row loads are issued before the first is
+// consumed.  A lane covers V adjacent columns per pass (a 4-byte bf16 pair
+// or an 8-byte float2 at V = 2), NC passes of 64 * V columns cover W.  At a
+// push the register pairs are permuted across lanes so that each atomic
+// instruction adds 64 consecutive floats (256 contiguous bytes).
+template <typename T, int V>
+struct RowPiece;
+
+template <>
+struct RowPiece<bf16_t, 2> {
+  typedef uint32_t raw_t;
+  static __device__ __forceinline__ void add(raw_t u, float* acc) {
+    acc[0] += bf2f((bf16_t)(u & 0xffffu));
+    acc[1] += bf2f((bf16_t)(u >> 16));
+  }
+};
+template <>
+struct RowPiece<bf16_t, 1> {
+  typedef bf16_t raw_t;
+  static __device__ __forceinline__ void add(raw_t u, float* acc) { acc[0] += bf2f(u); }
+};
+template <>
+struct RowPiece<float, 2> {
+  typedef float2 raw_t;
+  static __device__ __forceinline__ void add(raw_t u, float* acc) {
+    acc[0] += u.x;
+    acc[1] += u.y;
+  }
+};
+template <>
+struct RowPiece<float, 1> {
+  typedef float raw_t;
+  static __device__ __forceinline__ void add(raw_t u, float* acc) { acc[0] += u; }
+};
+
+template <int V, int NC>
+__device__ __forceinline__ void hashembed_merged_push(float* __restrict__ dT32,
+                                                      const int32_t* q, int W, int lane,
+                                                      float (&acc)[NC][V]) {
+#pragma unroll
+  for (int c = 0; c < NC; c++) {
+    if constexpr (V == 2) {
+      // lane l holds columns c*128 + 2l and 2l + 1; hand out columns
+      // c*128 + l and c*128 + 64 + l instead
+      const float lo0 = __shfl(acc[c][0], lane >> 1, SRX_WAVE);
+      const float lo1 = __shfl(acc[c][V - 1], lane >> 1, SRX_WAVE);
+      const float hi0 = __shfl(acc[c][0], 32 + (lane >> 1), SRX_WAVE);
+      const float hi1 = __shfl(acc[c][V - 1], 32 + (lane >> 1), SRX_WAVE);
+      const float lo = (lane & 1) ? lo1 : lo0;
+      const float hi = (lane & 1) ? hi1 : hi0;
+      const int w = c * 128 + lane;
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        float* row = dT32 + (long)q[s] * W;
+        if (w < W) atomicAdd(row + w, lo);
+        if (w + 64 < W) atomicAdd(row + w + 64, hi);
+      }
+    } else {
+      const int w = c * 64 + lane;
+#pragma unroll
+      for (int s = 0; s < 4; s++)
+        if (w < W) atomicAdd(dT32 + (long)q[s] * W + w, acc[c][0]);
+    }
+#pragma unroll
+    for (int v = 0; v < V; v++) acc[c][v] = 0.f;
+  }
+}
+
+template <typename T, int V, int NC, int U>
+__global__ void hashembed_bwd_merged_kernel(const int64_t* __restrict__ order,
+                                            const int32_t* __restrict__ rows,
+                                            const T* __restrict__ dY,
+                                            float* __restrict__ dT32,
+                                            long nT, int W, long ldY) {
+  constexpr int CHUNK = 2 * SRX_WAVE;
+  typedef typename RowPiece<T, V>::raw_t raw_t;
+  const int lane = threadIdx.x & (SRX_WAVE - 1);
+  const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) / SRX_WAVE;
+  const long c0 = wave * CHUNK;
+  if (c0 >= nT) return;
+  const int n = (int)min((long)CHUNK, nT - c0);  // wave-uniform, >= 1
+  float acc[NC][V];
+#pragma unroll
+  for (int c = 0; c < NC; c++)
+#pragma unroll
+    for (int v = 0; v < V; v++) acc[c][v] = 0.f;
+  int32_t cur[4] = {0, 0, 0, 0};
+  bool open = false;
+#pragma unroll
+  for (int half = 0; half < 2; half++) {
+    const int base = half * SRX_WAVE;
+    if (base >= n) break;
+    // positions past the chunk's end repeat its first entry: their loads
+    // stay in bounds and their values are never added
+    const long pos = c0 + (base + lane < n ? base + lane : 0);
+    const int tok = (int)order[pos];
+    const int4 quad = *(const int4*)(rows + (long)tok * 4);
+    for (int b = 0; b < SRX_WAVE; b += U) {
+      if (base + b >= n) break;
+      raw_t v[U][NC];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int tu = __builtin_amdgcn_readlane(tok, b + u);
+        const T* src = dY + (long)tu * ldY;
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+          const int w = (c * SRX_WAVE + lane) * V;
+          v[u][c] = *(const raw_t*)(src + (w < W ? w : 0));
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        if (base + b + u < n) {
+          int32_t q[4];
+          q[0] = __builtin_amdgcn_readlane(quad.x, b + u);
+          q[1] = __builtin_amdgcn_readlane(quad.y, b + u);
+          q[2] = __builtin_amdgcn_readlane(quad.z, b + u);
+          q[3] = __builtin_amdgcn_readlane(quad.w, b + u);
+          const bool same = q[0] == cur[0] && q[1] == cur[1] && q[2] == cur[2] &&
+                            q[3] == cur[3];
+          if (!open || !same) {
+            if (open) hashembed_merged_push<V, NC>(dT32, cur, W, lane, acc);
+            cur[0] = q[0]; cur[1] = q[1]; cur[2] = q[2]; cur[3] = q[3];
+            open = true;
+          }
+#pragma unroll
+          for (int c = 0; c < NC; c++) RowPiece<T, V>::add(v[u][c], acc[c]);
+        }
+      }
+    }
+  }
+  if (open) hashembed_merged_push<V, NC>(dT32, cur, W, lane, acc);
+}
+
 // ------------------------------------------------- parser step scorer
 // One wave per state (SURVEY.md §2.5 parser_step_score): gather nF
 // precomputed rows (pieces-major [T+1, nF, 2*H]), sum + bias, maxout P=2.

@@ -304,6 +304,110 @@ at::Tensor hashembed_bwd(at::Tensor dY, at::Tensor rows, int64_t nrows) {
   return dT32.to(dY.scalar_type());
 }
 
+// All n tables in one launch (multi_hashembed_fwd_kernel): writes column
+// blocks [col_off, col_off + n W) of X [nT, ldX] and returns rows [n, nT, 4]
+// and the int32 sort keys [n, nT].  Fast path only — equal W across tables,
+// W a multiple of 8, bf16 or fp32; the caller uses the per-table launches
+// for anything else.
+std::vector<at::Tensor> multi_hashembed_fwd(at::Tensor ids4,
+                                            std::vector<at::Tensor> tables,
+                                            std::vector<int64_t> seeds, at::Tensor X,
+                                            int64_t col_off) {
+  const int n = (int)tables.size();
+  TORCH_CHECK(n >= 1 && n <= SRX_MHE_MAX_TABLES, "multi_hashembed_fwd: 1..",
+              SRX_MHE_MAX_TABLES, " tables");
+  TORCH_CHECK((int)seeds.size() == n, "multi_hashembed_fwd: one seed per table");
+  TORCH_CHECK(ids4.is_cuda() && ids4.dim() == 2 && ids4.scalar_type() == at::kLong &&
+                  ids4.size(1) >= n && (ids4.stride(1) == 1 || ids4.size(1) == 1),
+              "ids4 must be a GPU int64 [T, >= n] row view");
+  const long nT = ids4.size(0);
+  const int W = (int)tables[0].size(1);
+  const auto dtype = tables[0].scalar_type();
+  TORCH_CHECK(W % 8 == 0, "multi_hashembed_fwd: W % 8 == 0");
+  MultiHashTables tabs;
+  for (int i = 0; i < SRX_MHE_MAX_TABLES; i++) {
+    const at::Tensor& tb = tables[i < n ? i : 0];
+    check_dev(tb);
+    TORCH_CHECK(tb.dim() == 2 && tb.size(1) == W && tb.scalar_type() == dtype &&
+                    tb.size(0) >= 1 && tb.size(0) < 2147483648L,
+                "multi_hashembed_fwd: tables must share W and dtype");
+    TORCH_CHECK((uintptr_t)tb.data_ptr() % 16 == 0, "table not 16-byte aligned");
+    tabs.table[i] = tb.data_ptr();
+    tabs.seed[i] = (uint32_t)seeds[i < n ? i : 0];
+    tabs.nrows[i] = (int32_t)tb.size(0);
+  }
+  TORCH_CHECK(X.is_cuda() && X.dim() == 2 && X.is_contiguous() && X.size(0) == nT &&
+                  X.scalar_type() == dtype,
+              "X must be a contiguous GPU [T, ldX] matrix of the tables' dtype");
+  const long ldX = X.size(1);
+  TORCH_CHECK(col_off >= 0 && col_off + (long)n * W <= ldX,
+              "multi_hashembed_fwd: column blocks outside X");
+  auto rows = at::empty({(long)n, nT, 4L}, X.options().dtype(at::kInt));
+  auto keys = at::empty({(long)n, nT}, X.options().dtype(at::kInt));
+  if (nT == 0) return {rows, keys};
+  auto stream = at::cuda::getCurrentCUDAStream();
+  DISPATCH_F(dtype, {
+    const long items = nT * n * (W / kVec);
+    TORCH_CHECK(items < 2147483648L, "multi_hashembed_fwd: T * n * W too large");
+    TORCH_CHECK(ldX % kVec == 0 && col_off % kVec == 0 &&
+                    (uintptr_t)X.data_ptr() % 16 == 0,
+                "multi_hashembed_fwd: X blocks not 16-byte aligned");
+    hipLaunchKernelGGL((multi_hashembed_fwd_kernel<scalar_t, kVec>),
+                       dim3((unsigned)((items + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       stream, tabs, (const uint64_t*)ids4.data_ptr<int64_t>(),
+                       (scalar_t*)X.data_ptr() + col_off, rows.data_ptr<int32_t>(),
+                       keys.data_ptr<int32_t>(), nT, n, W, (long)ids4.stride(0), ldX);
+  });
+  return {rows, keys};
+}
+
+// dT32 [R, W] fp32 (zero-initialised by the caller) += the HashEmbed table
+// gradient of dY, tokens visited in `order` (the int64 argsort of the
+// forward's sort keys, taken as torch returns it).  dY is a row view
+// (innermost stride 1, any row stride).
+void hashembed_bwd_merged(at::Tensor order, at::Tensor rows, at::Tensor dY,
+                          at::Tensor dT32) {
+  TORCH_CHECK(dY.is_cuda() && dY.dim() == 2 && dY.stride(1) == 1,
+              "dY must be a GPU row view (innermost stride 1)");
+  const long nT = dY.size(0);
+  const int W = (int)dY.size(1);
+  const long ldY = dY.stride(0);
+  TORCH_CHECK(W >= 1 && W <= 1024, "hashembed_bwd_merged W <= 1024");
+  TORCH_CHECK(nT < 2147483648L, "hashembed_bwd_merged T < 2^31");
+  check_dev(order);
+  check_dev(rows);
+  check_dev(dT32);
+  TORCH_CHECK(order.scalar_type() == at::kLong && order.numel() == nT,
+              "order must be int64 [T]");
+  TORCH_CHECK(rows.scalar_type() == at::kInt && rows.numel() == nT * 4 &&
+                  (uintptr_t)rows.data_ptr() % 16 == 0,
+              "rows must be int32 [T, 4], 16-byte aligned");
+  TORCH_CHECK(dT32.scalar_type() == at::kFloat && dT32.dim() == 2 && dT32.size(1) == W,
+              "dT32 must be fp32 [R, W]");
+  if (nT == 0) return;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const long waves = (nT + 2 * SRX_WAVE - 1) / (2 * SRX_WAVE);
+  const dim3 grid((unsigned)((waves * SRX_WAVE + kBlock - 1) / kBlock));
+#define SRX_HE_MERGED(V_, NC_, U_)                                                  \
+  hipLaunchKernelGGL((hashembed_bwd_merged_kernel<scalar_t, V_, NC_, U_>), grid,    \
+                     dim3(kBlock), 0, stream, order.data_ptr<int64_t>(),            \
+                     rows.data_ptr<int32_t>(), (const scalar_t*)dY.data_ptr(),      \
+                     dT32.data_ptr<float>(), nT, W, ldY)
+  DISPATCH_F(dY.scalar_type(), {
+    (void)kVec;
+    // paired accesses need every row piece aligned to 2 elements
+    const bool pairs = W % 2 == 0 && ldY % 2 == 0 &&
+                       (uintptr_t)dY.data_ptr() % (2 * sizeof(scalar_t)) == 0;
+    if (pairs && W <= 128)
+      SRX_HE_MERGED(2, 1, 8);
+    else if (pairs)
+      SRX_HE_MERGED(2, 8, 4);
+    else
+      SRX_HE_MERGED(1, 16, 2);
+  });
+#undef SRX_HE_MERGED
+}
+
 // ----------------------------------------------------- parser step score
 std::vector<at::Tensor> parser_step_fwd(at::Tensor pre, at::Tensor feats, at::Tensor bias) {
   check_dev(pre);
@@ -1521,6 +1625,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hashembed_fwd", &hashembed_fwd, py::arg("table"), py::arg("ids"),
         py::arg("seed"), py::arg("out") = py::none(), py::arg("col_off") = 0);
   m.def("hashembed_bwd", &hashembed_bwd);
+  m.def("multi_hashembed_fwd", &multi_hashembed_fwd, py::arg("ids4"),
+        py::arg("tables"), py::arg("seeds"), py::arg("X"), py::arg("col_off") = 0);
+  m.def("hashembed_bwd_merged", &hashembed_bwd_merged, py::arg("order"),
+        py::arg("rows"), py::arg("dY"), py::arg("dT32"));
   m.def("parser_step_fwd", &parser_step_fwd);
   m.def("parser_step_bwd", &parser_step_bwd);
   m.def("parser_step_bwd_into", &parser_step_bwd_into);

@@ -269,9 +269,84 @@ def bench_static_vectors():
         timeit_events(f"composed dW {tag}", composed_dw)
 
 
+def bench_hashembed():
+    """MultiHashEmbed forward and backward, per-table path against the fused
+    forward (multi_hashembed_fwd) and the token-sorted merged backward
+    (hashembed_bwd_merged), sort and glue included on both sides.  T = 1M,
+    W = 96, tables of 5000 / 2500 / 2500 / 2500 rows; Zipf ids over 5000
+    types (the bench.py corpus) and over 100k types (real text: fewer
+    tokens share an id, so fewer rows merge)."""
+    import numpy as np
+
+    T, W = 1 << 20, 96
+    nrows = (5000, 2500, 2500, 2500)
+    n = len(nrows)
+    seeds = [1, 2, 3, 4]
+    rng = np.random.default_rng(0)
+    tables = [(torch.randn(R, W, device=dev) * 0.1).to(torch.bfloat16)
+              for R in nrows]
+    dX = (torch.randn(T, n * W, device=dev) * 0.1).to(torch.bfloat16)
+    X = torch.empty(T, n * W, device=dev, dtype=torch.bfloat16)
+    for n_types in (5000, 100000):
+        p = 1.0 / np.arange(1, n_types + 1)
+        cols = []
+        for _ in range(n):
+            types = rng.integers(1, 2 ** 62, n_types, dtype=np.int64)
+            cols.append(types[rng.choice(n_types, size=T, p=p / p.sum())])
+        ids4 = torch.from_numpy(np.stack(cols, axis=1)).to(dev)
+
+        def fwd_old():
+            return [hip.hashembed_fwd(t, ids4[:, i].contiguous(), seeds[i],
+                                      X, i * W)[1]
+                    for i, t in enumerate(tables)]
+
+        def fwd_new():
+            return hip.multi_hashembed_fwd(ids4, tables, seeds, X, 0)
+
+        rows_old = fwd_old()
+        rows_new, keys_new = fwd_new()
+
+        def bwd_old():
+            out = []
+            for i, rows in enumerate(rows_old):
+                dst = rows.reshape(-1)
+                order = torch.argsort(dst)
+                dst_sorted = dst[order].contiguous().int()
+                src = (order // 4).int()
+                dT32 = torch.zeros(nrows[i], W, dtype=torch.float32, device=dev)
+                hip.seg_scatter_add(dst_sorted, src, dX[:, i * W:(i + 1) * W],
+                                    dT32)
+                out.append(dT32.to(torch.bfloat16))
+            return out
+
+        def bwd_new():
+            out = []
+            for i in range(n):
+                order = torch.argsort(keys_new[i])
+                dT32 = torch.zeros(nrows[i], W, dtype=torch.float32, device=dev)
+                hip.hashembed_bwd_merged(order, rows_new[i],
+                                         dX[:, i * W:(i + 1) * W], dT32)
+                out.append(dT32.to(torch.bfloat16))
+            return out
+
+        def bwd_new_kernel_only(orders=[torch.argsort(k) for k in keys_new]):
+            for i in range(n):
+                dT32 = torch.zeros(nrows[i], W, dtype=torch.float32, device=dev)
+                hip.hashembed_bwd_merged(orders[i], rows_new[i],
+                                         dX[:, i * W:(i + 1) * W], dT32)
+
+        tag = f"(T=1M,W=96,{n_types} types)"
+        timeit_events(f"hashembed fwd x4 per-table {tag}", fwd_old)
+        timeit_events(f"multi_hashembed_fwd {tag}", fwd_new)
+        timeit_events(f"hashembed bwd x4 seg_scatter {tag}", bwd_old)
+        timeit_events(f"hashembed bwd x4 merged {tag}", bwd_new)
+        timeit_events(f"  merged kernels alone {tag}", bwd_new_kernel_only)
+
+
 ALL = {"mwe": bench_mwe, "dpre": bench_dpre, "ce": bench_ce,
        "gpustate": bench_gpustate, "attn": bench_attn,
-       "static_vectors": bench_static_vectors}
+       "static_vectors": bench_static_vectors,
+       "hashembed": bench_hashembed}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(ALL)
