@@ -211,10 +211,11 @@ def init_config_cli(
 @init_app.command("vectors")
 def init_vectors_cli(
     lang: str = typer.Argument(..., help="Language code of the pipeline"),
-    vectors_loc: Path = typer.Argument(..., help="word2vec text file (.txt or .txt.gz)"),
+    vectors_loc: Path = typer.Argument(..., help="word2vec text file, or a .floret table with --mode floret (.gz too)"),
     output_dir: Path = typer.Argument(..., help="Pipeline directory to write"),
     truncate: int = typer.Option(0, "--truncate", "-t", help="Keep only the first N vectors (0 = all)"),
     name: str = typer.Option("", "--name", "-n", help="Name of the table (default: <lang>_vectors)"),
+    mode: str = typer.Option("default", "--mode", "-m", help="'default': word2vec text, one row per word; 'floret': a .floret hashed n-gram table"),
 ):
     """Convert word vectors to a loadable pipeline directory that holds only
     a vocab with vectors (the `spacy init vectors` role).  Point
@@ -223,7 +224,7 @@ def init_vectors_cli(
 
     try:
         nlp = init_vectors(lang, vectors_loc, output_dir, truncate=truncate,
-                           name=name or None)
+                           name=name or None, mode=mode)
     except ValueError as e:
         raise SystemExit(f"[x] {e}")
     print(f"[+] wrote {output_dir}: {nlp.vocab.vectors!r}")

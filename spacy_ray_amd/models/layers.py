@@ -64,9 +64,19 @@ class StaticVectors(nn.Module):
         super().__init__()
         self.nO, self.nM, self.key_attr = nO, nM, key_attr
         self.W = nn.Parameter(glorot_uniform_(torch.empty(nO, nM)))
+        self._check_key_attr(vectors)
         self.__dict__["vectors"] = vectors
 
+    def _check_key_attr(self, vectors) -> None:
+        if vectors is not None and vectors.is_floret:
+            from spacy_ray_amd.vocab.vectors import floret_key_attr_error
+
+            err = floret_key_attr_error(self.key_attr)
+            if err:
+                raise ValueError(err)
+
     def bind(self, vectors) -> None:
+        self._check_key_attr(vectors)
         if vectors.width != self.nM:
             raise ValueError(
                 f"StaticVectors was built for {self.nM}-dimensional vectors "
@@ -81,9 +91,18 @@ class StaticVectors(nn.Module):
                 "nlp.vocab.vectors ([initialize] vectors = <path>)")
         return self.vectors.device_table(self.W.device, self.W.dtype)
 
+    def table_and_rows(self, batch):
+        """(table, rows) for ops.static_vectors / ops.multi_hashembed.  In
+        floret mode the table is the batch's temporary one (a vector per
+        distinct word) and the rows are the token -> word map."""
+        if self.vectors is not None and self.vectors.is_floret:
+            return batch.get_floret_table(self.vectors, self.key_attr,
+                                          self.W.device, self.W.dtype)
+        return self.table(), batch.get_vec_rows(self.key_attr)
+
     def forward(self, batch) -> torch.Tensor:
-        return ops.static_vectors(self.W, self.table(),
-                                  batch.get_vec_rows(self.key_attr))
+        table, rows = self.table_and_rows(batch)
+        return ops.static_vectors(self.W, table, rows)
 
 
 class Linear(nn.Module):

@@ -64,7 +64,7 @@ class MultiHashEmbed(nn.Module):
             sv = self.static_vectors
             vectors = None
             if sv is not None:
-                vectors = (sv.table(), batch.get_vec_rows(sv.key_attr), sv.W)
+                vectors = (*sv.table_and_rows(batch), sv.W)
             X = ops.multi_hashembed(batch.attr_ids, self.seeds,
                                     list(self.tables), vectors)
         with timing.phase("t2v/mixer_gemm"):

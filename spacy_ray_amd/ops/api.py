@@ -449,6 +449,57 @@ def multi_hashembed_vectors(ids4: torch.Tensor, seeds, tables,
                       static_vectors(vW, vtable, vrows)], dim=1)
 
 
+# -------------------------------------------------------- floret vectors
+# floret_words_mean kernel (srx_floret.hip.h) against the composed path
+# (index_select + segment sum + divide): the same rule and the same switch as
+# the static-vectors kernels above, SRX_STATIC_VECTORS=fused / composed.
+# Measured (tools/kbench.py floret; R = 200k, nM = 300, U = 50k words): 0.076
+# ms against 1.918 ms at 0.96M entries, 0.163 against 3.275 ms at 1.62M.
+FLORET_MEAN_FUSED_DEFAULT = True
+
+
+def floret_words_mean_available(table: torch.Tensor) -> bool:
+    """The kernel needs a contiguous bf16 table whose row stride is a
+    multiple of 8 (every device copy of a Vectors table is), and the
+    extension."""
+    return (
+        table.is_cuda
+        and table.dtype == torch.bfloat16
+        and table.dim() == 2
+        and table.shape[1] >= 8
+        and table.shape[1] % 8 == 0
+        and table.is_contiguous()
+        and hip_ext() is not None
+    )
+
+
+def floret_words_mean(table: torch.Tensor, offsets: torch.Tensor,
+                      idx: torch.Tensor) -> torch.Tensor:
+    """One vector per distinct word of a floret batch: table [R, C], CSR
+    (offsets int32 [U + 1], idx int32 [nnz]) -> [U, C] in the table's
+    dtype, row u = mean of table[idx[offsets[u] : offsets[u + 1]]].  The
+    result is data (no autograd): it stands where the Vectors device table
+    does in static_vectors / multi_hashembed."""
+    mode = os.environ.get("SRX_STATIC_VECTORS", "")
+    if mode not in ("", "fused", "composed"):
+        raise ValueError(
+            f"SRX_STATIC_VECTORS={mode!r}: expected 'fused' or 'composed'")
+    table = table.detach()
+    fused = False
+    if mode != "composed" and table.is_cuda:
+        _want_hip(table)  # a GPU run without the extension is an error
+        fused = (floret_words_mean_available(table)
+                 and (mode == "fused" or FLORET_MEAN_FUSED_DEFAULT))
+    if not fused:
+        with torch.no_grad():
+            return ref.floret_words_mean(table, offsets, idx)
+    offsets = _rows_i32(offsets).contiguous()
+    idx = _rows_i32(idx).contiguous()
+    out = table.new_empty(offsets.numel() - 1, table.shape[1])
+    hip_ext().floret_words_mean(table, offsets, idx, out)
+    return out
+
+
 # ------------------------------------------------------------- layernorm
 class _LayerNorm(torch.autograd.Function):
     @staticmethod

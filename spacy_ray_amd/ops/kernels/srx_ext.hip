@@ -16,6 +16,7 @@
 #include "srx_softmax_reduce.hip.h"
 #include "srx_mwe.hip.h"
 #include "srx_staticvec.hip.h"
+#include "srx_floret.hip.h"
 #include "srx_activations.hip.h"
 #include "srx_attn.hip.h"
 
@@ -1504,6 +1505,53 @@ at::Tensor static_vectors_bwd_dw(at::Tensor table, at::Tensor rows, at::Tensor d
   return dW;
 }
 
+// ------------------------------------------------------- floret vectors
+// see srx_floret.hip.h.  out[u] = mean of table[idx[offsets[u] : offsets[u+1]]]
+// for u < U = offsets.numel() - 1; rows >= U of `out` are left alone.
+void floret_words_mean(at::Tensor table, at::Tensor offsets, at::Tensor idx,
+                       at::Tensor out) {
+  check_dev(table);
+  check_dev(offsets);
+  check_dev(idx);
+  check_dev(out);
+  TORCH_CHECK(table.scalar_type() == at::kBFloat16 && table.dim() == 2,
+              "floret_words_mean: table must be bf16 [R, nMp]");
+  TORCH_CHECK(offsets.scalar_type() == at::kInt && offsets.dim() == 1 &&
+                  offsets.numel() >= 1,
+              "floret_words_mean: offsets must be int32 [U + 1]");
+  TORCH_CHECK(idx.scalar_type() == at::kInt && idx.dim() == 1,
+              "floret_words_mean: idx must be int32 [nnz]");
+  const long U = offsets.numel() - 1;
+  const long nMp = table.size(1);
+  TORCH_CHECK(nMp >= 8 && nMp % 8 == 0,
+              "floret_words_mean: table row stride must be a multiple of 8");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 && out.dim() == 2 &&
+                  out.size(1) == nMp && out.size(0) >= U,
+              "floret_words_mean: out must be bf16 [>= U, nMp] with "
+              "offsets.numel() == U + 1");
+  TORCH_CHECK(table.size(0) < (1L << 31) && idx.numel() < (1L << 31) &&
+                  U < (1L << 31),
+              "floret_words_mean: sizes must fit in int32");
+  if (U == 0) return;
+  const int wpb = SRX_FLORET_THREADS / SRX_WAVE;
+  // memory bound: at most 8 workgroups per CU, the rest is grid-strided
+  const long cap = 8L * at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  dim3 grid((unsigned)std::min<long>((U + wpb - 1) / wpb, cap));
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const long Q = nMp / 8;
+#define SRX_FLORET_LAUNCH(SW)                                                  \
+  hipLaunchKernelGGL((floret_words_mean_kernel<SW>), grid,                     \
+                     dim3(SRX_FLORET_THREADS), 0, stream,                      \
+                     (const bf16_t*)table.data_ptr(), offsets.data_ptr<int>(), \
+                     idx.data_ptr<int>(), (bf16_t*)out.data_ptr(), (int)U,     \
+                     (int)table.size(0), (int)nMp, (int)idx.numel())
+  if (Q <= 8) SRX_FLORET_LAUNCH(8);
+  else if (Q <= 16) SRX_FLORET_LAUNCH(16);
+  else if (Q <= 32) SRX_FLORET_LAUNCH(32);
+  else SRX_FLORET_LAUNCH(64);
+#undef SRX_FLORET_LAUNCH
+}
+
 // --------------------------------------------- fused transition step (C++)
 // One python call per transition step: state scorer kernel + upper GEMM +
 // on-device action selection, with a C++ autograd node so the per-step
@@ -1657,6 +1705,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("static_vectors_bwd_dw", &static_vectors_bwd_dw, py::arg("table"),
         py::arg("rows"), py::arg("dX"), py::arg("col_off"), py::arg("nO"),
         py::arg("max_groups") = 0, py::arg("nM") = 0);
+  m.def("floret_words_mean", &floret_words_mean, py::arg("table"),
+        py::arg("offsets"), py::arg("idx"), py::arg("out"));
   m.def("fused_step", &fusedstep::fused_step);
   m.def("fused_entries_take", &fusedstep::fused_entries_take);
   m.def("transition_ce", &transition_ce, py::arg("scores"), py::arg("gold"),

@@ -112,6 +112,28 @@ def static_vectors_backward(dY: torch.Tensor, table: torch.Tensor,
     return dY.masked_fill((rows < 0)[:, None], 0).t().mm(G)
 
 
+def floret_words_mean(table: torch.Tensor, offsets: torch.Tensor,
+                      idx: torch.Tensor) -> torch.Tensor:
+    """table [R, C], CSR (offsets int [U + 1], ascending; idx int [nnz]) ->
+    [U, C] in the table's dtype: row u is the fp32 mean of table[idx[
+    offsets[u] : offsets[u + 1]]], zero for an empty slice.  index_select to
+    fp32, a segment sum (torch.segment_reduce: one sequential sum per
+    segment, no atomics, so the result is reproducible), a divide, a cast.
+    Entries outside [0, R) contribute zero and offsets are clamped to
+    [0, nnz], as in the kernel (srx_floret.hip.h)."""
+    R = table.shape[0]
+    nnz = idx.numel()
+    bounds = offsets.long().clamp(0, nnz)
+    counts = (bounds[1:] - bounds[:-1]).clamp_(min=0)
+    idx = idx.long()
+    bad = (idx < 0) | (idx >= R)
+    G = table.index_select(0, idx.clamp(0, max(R - 1, 0))).float()
+    G = G.masked_fill(bad[:, None], 0)
+    sums = torch.segment_reduce(G, "sum", offsets=bounds, axis=0, unsafe=True)
+    mean = sums / counts.clamp(min=1)[:, None].float()
+    return mean.to(table.dtype)
+
+
 def layernorm(X: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float = 1e-5):
     mu = X.mean(dim=-1, keepdim=True)
     var = X.var(dim=-1, unbiased=False, keepdim=True)

@@ -465,15 +465,31 @@ def load_init_vectors(nlp: Language, cfg: Dict) -> None:
 
 
 def init_vectors(lang: str, vectors_loc, output_dir, *, truncate: int = 0,
-                 name: Optional[str] = None) -> Language:
-    """word2vec text file -> a pipeline directory with an empty pipeline
-    and a vocab that holds the vectors (`spacy-mi init vectors`)."""
-    from spacy_ray_amd.vocab.vectors import Vectors, read_word2vec_text
+                 name: Optional[str] = None, mode: str = "default",
+                 key_attr: str = "ORTH") -> Language:
+    """word2vec text file (mode "default") or floret's `.floret` table
+    (mode "floret") -> a pipeline directory with an empty pipeline and a
+    vocab that holds the vectors (`spacy-mi init vectors`)."""
+    from spacy_ray_amd.vocab.vectors import (
+        MODES, Vectors, read_floret_text, read_word2vec_text)
 
-    words, data = read_word2vec_text(vectors_loc, truncate=truncate)
+    if mode not in MODES:
+        raise ValueError(f"init vectors --mode must be one of {MODES}, got {mode!r}")
     config = Config.from_str(f'[nlp]\nlang = "{lang}"\npipeline = []\n')
+    if mode == "floret":
+        if truncate:
+            raise ValueError(
+                "--truncate cannot be used with --mode floret: every row of "
+                "a hashed n-gram table is needed")
+        data, settings = read_floret_text(vectors_loc)
+        nlp = build_nlp(config)
+        nlp.vocab.vectors = Vectors(data, mode="floret", key_attr=key_attr,
+                                    name=name or f"{lang}_vectors", **settings)
+        nlp.to_disk(output_dir)
+        return nlp
+    words, data = read_word2vec_text(vectors_loc, truncate=truncate)
     nlp = build_nlp(config)
-    nlp.vocab.vectors = Vectors.from_words(words, data,
+    nlp.vocab.vectors = Vectors.from_words(words, data, key_attr=key_attr,
                                            name=name or f"{lang}_vectors")
     for w in words:
         nlp.vocab.strings.add(w)
@@ -507,8 +523,18 @@ def check_static_vectors_config(cfg: Dict) -> List[str]:
         return []
     from spacy_ray_amd.vocab.vectors import load_vectors_dir
 
-    vectors = load_vectors_dir(path)
+    try:
+        vectors = load_vectors_dir(path)
+    except ValueError as e:
+        # e.g. a floret table whose vectors.json names key_attr = "NORM"
+        raise ValueError(f"[initialize] vectors = {path}: {e}") from None
     lines = [f"vectors OK: {vectors!r}"]
+    if vectors.is_floret:
+        lines.append(
+            f"floret vectors: no out-of-vocabulary words; each batch averages "
+            f"the n-gram rows of its distinct words (n = {vectors.minn}.."
+            f"{vectors.maxn}, {vectors.hash_count} hashes per n-gram, keyed "
+            f"by {vectors.key_attr})")
     if not wants:
         lines.append("note: [initialize] vectors is set but no model has "
                      "include_static_vectors = true (Doc.vector only)")

@@ -40,6 +40,8 @@ class Vocab:
         return int(self.vectors.find_words([key])[0])
 
     def has_vector(self, word: str) -> bool:
+        if self.vectors is not None and self.vectors.is_floret:
+            return bool(word)  # floret: every non-empty string has n-grams
         return self._vector_row(word) >= 0
 
     def get_vector(self, word: str) -> np.ndarray:
@@ -47,6 +49,9 @@ class Vocab:
         is out of vocabulary or no vectors are loaded."""
         if self.vectors is None:
             return np.zeros(0, dtype=np.float32)
+        if self.vectors.is_floret:
+            key = word.lower() if self.vectors.key_attr != "ORTH" else word
+            return self.vectors.get_batch([key])[0]
         row = self._vector_row(word)
         if row < 0:
             return np.zeros(self.vectors.width, dtype=np.float32)
@@ -113,6 +118,11 @@ class Doc:
         if vectors is None:
             raise ValueError("the vocab has no vectors loaded")
         key_attr = key_attr or vectors.key_attr
+        if vectors.is_floret:
+            raise ValueError(
+                "Doc.get_vector_rows: floret vectors have no row per token; "
+                "the batch path is TokenBatch.get_floret_table (one averaged "
+                "row per distinct word), Doc.vector works as usual")
         cached = self.vector_rows.get(key_attr)
         if cached is not None and cached[0] is vectors:
             return cached[1]
@@ -125,12 +135,46 @@ class Doc:
         self.vector_rows[key_attr] = (vectors, rows)
         return rows
 
+    def vector_words(self, key_attr: str) -> List[str]:
+        """The strings a floret table hashes under `key_attr`."""
+        if key_attr == "ORTH":
+            return self.words
+        if key_attr == "LOWER":
+            return [w.lower() for w in self.words]
+        from .vectors import floret_key_attr_error
+
+        raise ValueError(floret_key_attr_error(key_attr))
+
+    def get_vector_keys(self, key_attr: str) -> np.ndarray:
+        """uint64 [n]: the hash of each token's string under `key_attr`, what
+        the floret batch path deduplicates over.  LOWER is column 0 of
+        attr_hashes (the lower-cased form); ORTH is hashed once per Doc and
+        kept with vector_rows."""
+        if key_attr == "LOWER":
+            return self.attr_hashes[:, 0]
+        if key_attr != "ORTH":
+            from .vectors import floret_key_attr_error
+
+            raise ValueError(floret_key_attr_error(key_attr))
+        cached = self.vector_rows.get("ORTH/keys")
+        if cached is None:
+            from .vectors import hash_words
+
+            cached = (None, hash_words(self.words))
+            self.vector_rows["ORTH/keys"] = cached
+        return cached[1]
+
     @property
     def vector(self) -> np.ndarray:
         """Mean of the in-vocabulary token vectors, or zeros."""
         vectors = self.vocab.vectors
         if vectors is None:
             return np.zeros(0, dtype=np.float32)
+        if vectors.is_floret:
+            words = [w for w in self.vector_words(vectors.key_attr) if w]
+            if not words:
+                return np.zeros(vectors.width, dtype=np.float32)
+            return vectors.get_batch(words).mean(axis=0)
         rows = self.get_vector_rows()
         rows = rows[rows >= 0]
         if not len(rows):

@@ -343,7 +343,119 @@ def bench_hashembed():
         timeit_events(f"  merged kernels alone {tag}", bwd_new_kernel_only)
 
 
+def _floret_lexicons(U):
+    """Two lexicons of U distinct words: the synthetic corpus vocabulary
+    (w0, w1, ...: short words, few n-grams) and pseudo-words whose lengths
+    follow a real lexicon's (types are longer than tokens: 2..24 letters,
+    mode 8)."""
+    import numpy as np
+
+    rng = np.random.default_rng(0)
+    synthetic = [f"w{i}" for i in range(U)]
+    lens = np.clip(rng.gamma(6.0, 1.5, size=U).round().astype(int), 2, 24)
+    letters = np.array(list("etaoinshrdlucmfwypvbgkqjxz"))
+    p = 1.0 / np.arange(1, 27)
+    p /= p.sum()
+    words, seen = [], set()
+    for i, n in enumerate(lens.tolist()):
+        w = "".join(rng.choice(letters, size=n, p=p))
+        if w in seen:
+            w += f"{i}"
+        seen.add(w)
+        words.append(w)
+    return {"synthetic vocab": synthetic, "real-length words": words}
+
+
+def bench_floret():
+    """floret_words_mean against the composed torch path (index_select +
+    segment sum + divide + cast) on the same inputs: R = 200000 rows, nM =
+    300 (row stride 320), U = 50000 distinct words, minn = 4, maxn = 5,
+    hash_count = 2.  The two paths alternate inside one timed loop.  Also
+    prints the achieved read rate over the floor nnz * nMp * 2 bytes, the
+    largest difference between the two results, and the host cost of
+    building a 1M-token floret batch (dedupe + n-gram expansion)."""
+    import numpy as np
+
+    from spacy_ray_amd.ops import torch_ref as ref
+    from spacy_ray_amd.vocab.vectors import Vectors
+
+    R, nM, nMp, U = 200_000, 300, 320, 50_000
+    rng = np.random.default_rng(0)
+    vectors = Vectors(np.zeros((R, 1), dtype=np.float32), mode="floret",
+                      minn=4, maxn=5, hash_count=2)
+    table = torch.zeros(R, nMp, device=dev, dtype=torch.bfloat16)
+    table[:, :nM] = torch.randn(R, nM, device=dev) * 0.5
+    lexicons = _floret_lexicons(U)
+    for tag, words in lexicons.items():
+        offsets_np, idx_np = vectors.ngram_rows(words)
+        nnz = int(idx_np.shape[0])
+        counts = np.diff(offsets_np)
+        offsets = torch.from_numpy(offsets_np).to(dev)
+        idx = torch.from_numpy(idx_np).to(dev)
+        out = torch.empty(U, nMp, device=dev, dtype=torch.bfloat16)
+        print(f"floret {tag}: U = {U}, nnz = {nnz}, entries per word median "
+              f"{int(np.median(counts))} max {int(counts.max())}")
+
+        def fused():
+            hip.floret_words_mean(table, offsets, idx, out)
+
+        def composed():
+            return ref.floret_words_mean(table, offsets, idx)
+
+        fused()
+        diff = (out.float() - composed().float()).abs().max().item()
+        # alternate the two so that clock and cache state are shared
+        for _ in range(10):
+            fused()
+            composed()
+        torch.cuda.synchronize()
+        times = {"fused": [], "composed": []}
+        for _ in range(30):
+            for name, fn in (("fused", fused), ("composed", composed)):
+                a = torch.cuda.Event(enable_timing=True)
+                b = torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                times[name].append(a.elapsed_time(b))
+        floor_bytes = nnz * nMp * 2
+        for name, ts in times.items():
+            ts.sort()
+            med = ts[len(ts) // 2]
+            print(f"  floret_words_mean {name:9s} median {med:8.3f} ms  min "
+                  f"{ts[0]:8.3f} ms  {floor_bytes / med / 1e9:8.3f} TB/s of "
+                  f"row reads")
+        print(f"  max |fused - composed| = {diff:.3e}")
+
+    # host cost of one 1M-token floret batch, Zipf tokens over a 50k lexicon
+    from spacy_ray_amd.models.batch import TokenBatch
+    from spacy_ray_amd.vocab.doc import Doc, Vocab
+
+    words = lexicons["real-length words"]
+    vocab = Vocab("xx")
+    vocab.vectors = vectors
+    p = 1.0 / np.arange(1, U + 1)
+    ids = rng.choice(U, size=1 << 20, p=p / p.sum())
+    no_attrs = np.zeros((20, 4), dtype=np.uint64)  # not what is timed
+    docs = [Doc(vocab, [words[i] for i in ids[k:k + 20]], attr_hashes=no_attrs)
+            for k in range(0, 1 << 20, 20)]
+    batch = TokenBatch(docs, "cpu")
+    for d in docs:
+        d.get_vector_keys("ORTH")  # per-Doc hashes are cached, as in training
+    best = None
+    for _ in range(3):
+        t0 = time.perf_counter()
+        inverse, offsets_np, idx_np, distinct = batch._build_floret("ORTH")
+        ms = (time.perf_counter() - t0) * 1e3
+        best = ms if best is None else min(best, ms)
+    print(f"floret host batch build (T = {len(inverse)}, U = {len(distinct)}, "
+          f"nnz = {len(idx_np)}): {best:.1f} ms (dedupe + n-gram expansion, "
+          f"best of 3, token hashes cached per Doc)")
+
+
 ALL = {"mwe": bench_mwe, "dpre": bench_dpre, "ce": bench_ce,
+       "floret": bench_floret,
        "gpustate": bench_gpustate, "attn": bench_attn,
        "static_vectors": bench_static_vectors,
        "hashembed": bench_hashembed}
