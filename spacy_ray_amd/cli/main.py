@@ -483,7 +483,11 @@ def find_threshold_cli(
           f"`threshold = {best[0]:.3f}` on [components.{pipe_name}]")
 
 
-@app.command("pretrain")
+@app.command(
+    "pretrain",
+    # dotted config overrides (--paths.vectors=...), as in `ray train`
+    context_settings={"allow_extra_args": True, "ignore_unknown_options": True},
+)
 def pretrain_cli(
     ctx: typer.Context,
     config_path: Path = typer.Argument(..., help="Path to config file (its tok2vec + train corpus are used)"),
@@ -494,24 +498,46 @@ def pretrain_cli(
     mask_rate: float = typer.Option(0.15, "--mask-rate"),
     learn_rate: float = typer.Option(1e-3, "--lr"),
     use_gpu: int = typer.Option(-1, "--gpu-id", "-g", help="GPU ID or -1 for CPU"),
+    objective: Optional[str] = typer.Option(None, "--objective", help="masked (hash buckets, the default) or vectors (predict the static vector; needs [initialize] vectors)"),
+    loss: Optional[str] = typer.Option(None, "--loss", help="Vectors objective: cosine (default) or L2"),
+    hidden_size: Optional[int] = typer.Option(None, "--hidden-size", help="Vectors objective: maxout width of the head (default 300)"),
+    maxout_pieces: Optional[int] = typer.Option(None, "--maxout-pieces", help="Vectors objective: maxout pieces of the head (default 3)"),
 ):
-    """Pretrain the config's tok2vec with a masked-token objective on the
-    raw training corpus (the `spacy pretrain` role); load the result at
-    training time with `--init-tok2vec` / `training.init_tok2vec`."""
+    """Pretrain the config's tok2vec on the raw training corpus (the `spacy
+    pretrain` role) with the masked-token objective, or with the vectors
+    objective (`--objective vectors` or a `[pretraining.objective]` block;
+    flags override the block); load the result at training time with
+    `--init-tok2vec` / `training.init_tok2vec`."""
     from spacy_ray_amd.config.config import resolve_dot_names
     from spacy_ray_amd.pipeline.language import init_nlp
-    from spacy_ray_amd.train.pretrain import pretrain_tok2vec, save_tok2vec
+    from spacy_ray_amd.train.pretrain import (LOSSES, OBJECTIVES,
+                                              objective_from_config,
+                                              pretrain_tok2vec, save_tok2vec)
 
+    if objective is not None and objective not in OBJECTIVES:
+        raise SystemExit(f"[x] --objective must be one of {OBJECTIVES}, got {objective!r}")
+    if loss is not None and loss not in LOSSES:
+        raise SystemExit(f"[x] --loss must be one of {LOSSES}, got {loss!r}")
     overrides = parse_config_overrides(list(ctx.args))
     config = Config.from_disk(config_path, overrides=overrides)
+    icfg = config.interpolate()
+    try:
+        settings = objective_from_config(icfg)
+    except (ValueError, KeyError, TypeError) as e:
+        raise SystemExit(f"[x] [pretraining.objective]: {e}")
+    flags = {"objective": objective, "loss": loss, "hidden_size": hidden_size,
+             "maxout_pieces": maxout_pieces}
+    settings.update({k: v for k, v in flags.items() if v is not None})
     device = f"cuda:{use_gpu}" if use_gpu >= 0 else "cpu"
     nlp = init_nlp(config, device=device)
-    icfg = config.interpolate()
     dot = icfg.get("training", {}).get("train_corpus", "corpora.train")
     (corpus,) = resolve_dot_names(icfg, [dot])
-    losses = pretrain_tok2vec(nlp, corpus, steps=steps, batch_docs=batch_docs,
-                              n_buckets=n_buckets, mask_rate=mask_rate,
-                              learn_rate=learn_rate)
+    try:
+        losses = pretrain_tok2vec(nlp, corpus, steps=steps, batch_docs=batch_docs,
+                                  n_buckets=n_buckets, mask_rate=mask_rate,
+                                  learn_rate=learn_rate, **settings)
+    except ValueError as e:
+        raise SystemExit(f"[x] {e}")
     path = save_tok2vec(nlp, output_path)
     print(f"[+] wrote {path} (final loss {losses[-1]:.4f}) — train with "
           f"--init-tok2vec {output_path}")

@@ -71,6 +71,20 @@ def _vocab_for_build():
     return vocab
 
 
+@registry.architectures("spacy.PretrainVectors.v1")
+def make_pretrain_vectors(maxout_pieces: int = 3, hidden_size: int = 300,
+                          loss: str = "cosine"):
+    """`[pretraining.objective]`: predict each masked token's static vector.
+    Returns the keyword arguments that select it in
+    train.pretrain.pretrain_tok2vec (the head is built there, once the
+    tok2vec and the table widths are known)."""
+    if loss not in ("cosine", "L2"):
+        raise ValueError(
+            f"spacy.PretrainVectors.v1: loss must be 'cosine' or 'L2', got {loss!r}")
+    return {"objective": "vectors", "loss": loss,
+            "hidden_size": int(hidden_size), "maxout_pieces": int(maxout_pieces)}
+
+
 @registry.architectures("spacy.MaxoutWindowEncoder.v2")
 def make_maxout_window_encoder(
     width: int, depth: int = 4, window_size: int = 1, maxout_pieces: int = 3

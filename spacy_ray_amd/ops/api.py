@@ -500,6 +500,111 @@ def floret_words_mean(table: torch.Tensor, offsets: torch.Tensor,
     return out
 
 
+# ---------------------------------------------------------- vectors loss
+# vectors_loss kernel (srx_vecloss.hip.h) against the composed path
+# (torch_ref.vectors_loss: index_select, norms, elementwise passes): the
+# fused path is the default only where the tools/kbench.py measurement found
+# it not slower (profiles/README.md); SRX_VECTORS_LOSS=fused / composed
+# overrides the default either way.
+# Measured (tools/kbench.py vecloss; N = 150k, nM = 300, V = 200k; row
+# losses, their sum and dPred on both sides): cosine 0.090 ms against 1.569
+# ms, L2 0.076 ms against 0.876 ms.
+VECTORS_LOSS_FUSED_DEFAULT = True
+
+
+def vectors_loss_available(pred: torch.Tensor, table: torch.Tensor) -> bool:
+    """The kernel needs a bf16 pred [N, nM], the bf16 padded table ([V, nMp],
+    nMp = roundup(nM, 32) <= 320, contiguous, V >= 1) and the extension."""
+    if pred.dim() != 2 or table.dim() != 2:
+        return False
+    nM, nMp = pred.shape[1], table.shape[1]
+    return (
+        pred.is_cuda
+        and table.is_cuda
+        and pred.dtype == torch.bfloat16
+        and table.dtype == torch.bfloat16
+        and nMp % 32 == 0
+        and 32 <= nMp <= 320
+        and 0 <= nMp - nM < 32
+        and table.shape[0] >= 1
+        and table.is_contiguous()
+        and hip_ext() is not None
+    )
+
+
+def _vectors_loss_fused(pred: torch.Tensor, table: torch.Tensor) -> bool:
+    mode = os.environ.get("SRX_VECTORS_LOSS", "")
+    if mode not in ("", "fused", "composed"):
+        raise ValueError(
+            f"SRX_VECTORS_LOSS={mode!r}: expected 'fused' or 'composed'")
+    if mode == "composed" or not pred.is_cuda:
+        return False
+    _want_hip(pred)  # a GPU run without the extension is an error, as elsewhere
+    if not vectors_loss_available(pred, table):
+        return False
+    return mode == "fused" or VECTORS_LOSS_FUSED_DEFAULT
+
+
+class _VectorsLoss(torch.autograd.Function):
+    """scale * sum_i loss_i; dPred is computed with the loss and kept for the
+    backward, which only multiplies it by the incoming scalar.  The table is
+    data: no gradient flows to it."""
+
+    @staticmethod
+    def forward(ctx, pred, table, rows, loss, scale):
+        if _vectors_loss_fused(pred, table):
+            if pred.stride(1) != 1:
+                pred = pred.contiguous()
+            rows = _rows_i32(rows).contiguous()
+            row_loss = torch.empty(pred.shape[0], dtype=torch.float32,
+                                   device=pred.device)
+            dpred = torch.empty(pred.shape, dtype=pred.dtype, device=pred.device)
+            hip_ext().vectors_loss(pred, table, rows, row_loss, dpred,
+                                   loss == "L2", float(scale))
+        else:
+            row_loss, dpred = ref.vectors_loss(pred, table, rows, loss, scale)
+        ctx.save_for_backward(dpred)
+        return row_loss.sum() * scale
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return dpred * g.to(dpred.dtype), None, None, None, None
+
+
+def vectors_loss(pred: torch.Tensor, table: torch.Tensor, rows: torch.Tensor,
+                 *, loss: str = "cosine", scale: float = 1.0) -> torch.Tensor:
+    """Distance between predicted and static vectors (spaCy's
+    PretrainVectors objective).  pred [N, nM] is the head's output, table
+    the Vectors device table [V, nMp] (or a floret batch's temporary table
+    from TokenBatch.get_floret_table), rows int [N].  Returns the scalar
+    scale * sum_i loss_i in fp32 (fp64 for an fp64 pred) with autograd to
+    pred only; callers pass scale = 1 / N.
+
+    Per row, with p = pred[i] and y = table[rows[i], :nM]:
+
+    * skipped rows: rows[i] < 0, rows[i] >= V, and for the cosine also y
+      all zero (|y|^2 == 0) or |p|^2 == 0.  Loss 0, dPred row exactly zero,
+      and a non-finite p there reaches no output;
+    * loss="cosine" (thinc CosineDistance(normalize=True, ignore_zeros=True)):
+      c = p.y / (|p| |y|), loss_i = 1 - c,
+      dp = -scale (y / (|p| |y|) - c p / |p|^2);
+    * loss="L2" (thinc L2Distance, whose gradient has no factor 2):
+      loss_i = sum (p - y)^2, dp = scale (p - y).
+
+    On a GPU a bf16 pred against a bf16 table of width <= 320 runs as one
+    HIP launch (vectors_loss_available); fp32 preds, CPU tensors and other
+    shapes take the composed path.  SRX_VECTORS_LOSS=fused|composed
+    overrides the default."""
+    if loss not in ("cosine", "L2"):
+        raise ValueError(f"vectors_loss: loss={loss!r}: expected 'cosine' or 'L2'")
+    if pred.dim() != 2 or rows.dim() != 1 or rows.shape[0] != pred.shape[0]:
+        raise ValueError("vectors_loss: pred must be [N, nM] and rows [N]")
+    if table.dim() != 2 or table.shape[1] < pred.shape[1]:
+        raise ValueError("vectors_loss: table must be [V, >= nM]")
+    return _VectorsLoss.apply(pred, table.detach(), rows, loss, float(scale))
+
+
 # ------------------------------------------------------------- layernorm
 class _LayerNorm(torch.autograd.Function):
     @staticmethod

@@ -17,6 +17,7 @@
 #include "srx_mwe.hip.h"
 #include "srx_staticvec.hip.h"
 #include "srx_floret.hip.h"
+#include "srx_vecloss.hip.h"
 #include "srx_activations.hip.h"
 #include "srx_attn.hip.h"
 
@@ -1552,6 +1553,79 @@ void floret_words_mean(at::Tensor table, at::Tensor offsets, at::Tensor idx,
 #undef SRX_FLORET_LAUNCH
 }
 
+// ---------------------------------------------------------- vectors loss
+// see srx_vecloss.hip.h.  One launch: row_loss[i] (fp32) and dpred[i, :nM]
+// (bf16) for i < N = rows.numel(); rows >= N of either output and columns
+// >= nM of dpred are left alone.  pred and dpred may be row-strided views.
+void vectors_loss(at::Tensor pred, at::Tensor table, at::Tensor rows,
+                  at::Tensor row_loss, at::Tensor dpred, bool l2, double scale) {
+  check_dev(table);
+  check_dev(rows);
+  check_dev(row_loss);
+  TORCH_CHECK(table.scalar_type() == at::kBFloat16 && table.dim() == 2,
+              "vectors_loss: table must be bf16 [V, nMp]");
+  TORCH_CHECK(rows.scalar_type() == at::kInt && rows.dim() == 1,
+              "vectors_loss: rows must be int32 [N]");
+  const long N = rows.size(0);
+  const long nMp = table.size(1), V = table.size(0);
+  TORCH_CHECK(pred.is_cuda() && pred.scalar_type() == at::kBFloat16 &&
+                  pred.dim() == 2 && pred.size(0) == N,
+              "vectors_loss: pred must be bf16 [N, nM]");
+  const long nM = pred.size(1);
+  TORCH_CHECK(nMp % 32 == 0 && nMp >= 32 && nMp <= 320 && nM <= nMp &&
+                  nMp - nM < 32,
+              "vectors_loss: table row stride must be roundup(nM, 32) <= 320");
+  TORCH_CHECK(V >= 1 && V < (1L << 31), "vectors_loss: 1 <= V < 2^31");
+  TORCH_CHECK(aligned16(table.data_ptr()), "vectors_loss: table not 16-byte aligned");
+  TORCH_CHECK(dpred.is_cuda() && dpred.scalar_type() == at::kBFloat16 &&
+                  dpred.dim() == 2 && dpred.size(0) >= N && dpred.size(1) == nM,
+              "vectors_loss: dpred must be bf16 [>= N, nM]");
+  TORCH_CHECK(row_loss.scalar_type() == at::kFloat && row_loss.numel() >= N,
+              "vectors_loss: row_loss must be fp32 [>= N]");
+  if (N == 0) return;
+  // a one-row matrix may carry any row stride; it is never used
+  const long ldP = N > 1 ? pred.stride(0) : nM;
+  const long ldD = dpred.size(0) > 1 ? dpred.stride(0) : nM;
+  TORCH_CHECK(pred.stride(1) == 1 && dpred.stride(1) == 1 && ldP >= nM && ldD >= nM,
+              "vectors_loss: pred and dpred need unit column stride and "
+              "non-overlapping rows");
+  // widest access (in bf16 elements) that the base pointers, the row
+  // strides and the row length all allow
+  const uintptr_t mix = (uintptr_t)pred.data_ptr() | (uintptr_t)dpred.data_ptr() |
+                        (uintptr_t)(2 * ldP) | (uintptr_t)(2 * ldD) |
+                        (uintptr_t)(2 * nM);
+  const int pv = (mix % 16 == 0) ? 8 : (mix % 8 == 0) ? 4 : (mix % 4 == 0) ? 2 : 1;
+  const long Q = nMp / 8;
+  const int sw = Q <= 8 ? 8 : Q <= 16 ? 16 : Q <= 32 ? 32 : 64;
+  const long wpb = SRX_VECLOSS_THREADS / SRX_WAVE;
+  const long groups = (N + (SRX_WAVE / sw) - 1) / (SRX_WAVE / sw);
+  // memory bound: at most 8 workgroups per CU, the rest is grid-strided
+  const long cap = 8L * at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  dim3 grid((unsigned)std::min<long>((groups + wpb - 1) / wpb, cap));
+  auto stream = at::cuda::getCurrentCUDAStream();
+#define SRX_VECLOSS_LAUNCH(SW, PV)                                             \
+  hipLaunchKernelGGL((vectors_loss_kernel<SW, PV>), grid,                      \
+                     dim3(SRX_VECLOSS_THREADS), 0, stream,                     \
+                     (const bf16_t*)pred.data_ptr(),                           \
+                     (const bf16_t*)table.data_ptr(), rows.data_ptr<int>(),    \
+                     row_loss.data_ptr<float>(), (bf16_t*)dpred.data_ptr(),    \
+                     ldP, ldD, N, (int)V, (int)nM, (int)nMp, (int)l2,          \
+                     (float)scale)
+#define SRX_VECLOSS_PV(SW)                                                     \
+  switch (pv) {                                                                \
+    case 8: SRX_VECLOSS_LAUNCH(SW, 8); break;                                  \
+    case 4: SRX_VECLOSS_LAUNCH(SW, 4); break;                                  \
+    case 2: SRX_VECLOSS_LAUNCH(SW, 2); break;                                  \
+    default: SRX_VECLOSS_LAUNCH(SW, 1); break;                                 \
+  }
+  if (sw == 8) { SRX_VECLOSS_PV(8) }
+  else if (sw == 16) { SRX_VECLOSS_PV(16) }
+  else if (sw == 32) { SRX_VECLOSS_PV(32) }
+  else { SRX_VECLOSS_PV(64) }
+#undef SRX_VECLOSS_PV
+#undef SRX_VECLOSS_LAUNCH
+}
+
 // --------------------------------------------- fused transition step (C++)
 // One python call per transition step: state scorer kernel + upper GEMM +
 // on-device action selection, with a C++ autograd node so the per-step
@@ -1707,6 +1781,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("max_groups") = 0, py::arg("nM") = 0);
   m.def("floret_words_mean", &floret_words_mean, py::arg("table"),
         py::arg("offsets"), py::arg("idx"), py::arg("out"));
+  m.def("vectors_loss", &vectors_loss, py::arg("pred"), py::arg("table"),
+        py::arg("rows"), py::arg("row_loss"), py::arg("dpred"), py::arg("l2"),
+        py::arg("scale"));
   m.def("fused_step", &fusedstep::fused_step);
   m.def("fused_entries_take", &fusedstep::fused_entries_take);
   m.def("transition_ce", &transition_ce, py::arg("scores"), py::arg("gold"),

@@ -134,6 +134,51 @@ def floret_words_mean(table: torch.Tensor, offsets: torch.Tensor,
     return mean.to(table.dtype)
 
 
+def vectors_loss(pred: torch.Tensor, table: torch.Tensor, rows: torch.Tensor,
+                 loss: str = "cosine", scale: float = 1.0):
+    """pred [N, nM], table [V, >= nM], rows [N] int -> (row_loss [N] in the
+    compute type, dPred [N, nM] in pred's dtype), composed from torch ops;
+    the compute type is fp64 for an fp64 pred and fp32 otherwise.  With p =
+    pred[i] and y = table[rows[i], :nM]:
+
+    cosine  loss_i = 1 - c, c = p.y / (|p| |y|);
+            dp = -scale (y / (|p| |y|) - c p / |p|^2)
+    L2      loss_i = sum (p - y)^2;  dp = scale (p - y)   (no factor 2)
+
+    A row is skipped (loss 0, dPred row exactly zero) when rows[i] < 0 or
+    rows[i] >= V, and for the cosine also when |y|^2 == 0 or |p|^2 == 0.
+    The prediction of a skipped row is replaced before any arithmetic, so a
+    non-finite value there reaches no output.  The caller multiplies the sum
+    of row_loss by `scale`; dPred already carries it."""
+    if loss not in ("cosine", "L2"):
+        raise ValueError(f"vectors_loss: loss={loss!r}: expected 'cosine' or 'L2'")
+    ct = torch.float64 if pred.dtype == torch.float64 else torch.float32
+    V, nM = table.shape[0], pred.shape[1]
+    r = rows.long()
+    skip = (r < 0) | (r >= V)
+    y = table.index_select(0, r.clamp(0, max(V - 1, 0)))[:, :nM].to(ct)
+    p = pred.detach().to(ct)
+    if loss == "cosine":
+        yy = (y * y).sum(1)
+        skip = skip | (yy == 0) | ((p * p).sum(1) == 0)
+    # skipped rows compute on p = y = 1: finite, and thrown away below
+    p = torch.where(skip[:, None], torch.ones_like(p), p)
+    y = torch.where(skip[:, None], torch.ones_like(y), y)
+    if loss == "cosine":
+        pp = (p * p).sum(1, keepdim=True)
+        inv = 1.0 / (pp.sqrt() * (y * y).sum(1, keepdim=True).sqrt())
+        c = (p * y).sum(1, keepdim=True) * inv
+        row_loss = (1.0 - c)[:, 0]
+        dp = -scale * (y * inv - c * p / pp)
+    else:
+        d = p - y
+        row_loss = (d * d).sum(1)
+        dp = scale * d
+    row_loss = row_loss.masked_fill(skip, 0)
+    dp = dp.masked_fill(skip[:, None], 0)
+    return row_loss, dp.to(pred.dtype)
+
+
 def layernorm(X: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float = 1e-5):
     mu = X.mean(dim=-1, keepdim=True)
     var = X.var(dim=-1, unbiased=False, keepdim=True)

@@ -519,6 +519,15 @@ def check_static_vectors_config(cfg: Dict) -> List[str]:
             "include_static_vectors = true but [initialize] vectors is not "
             "set: point it (or [paths] vectors) at a directory written by "
             "`spacy-mi init vectors`")
+    objective = (cfg.get("pretraining") or {}).get("objective") or {}
+    wants_objective = (isinstance(objective, dict) and
+                       objective.get("@architectures") == "spacy.PretrainVectors.v1")
+    if wants_objective and not path:
+        raise ValueError(
+            "vectors objective without [initialize] vectors: "
+            "[pretraining.objective] is spacy.PretrainVectors.v1 but there "
+            "is no table to predict; point [initialize] vectors (or [paths] "
+            "vectors) at a directory written by `spacy-mi init vectors`")
     if not path:
         return []
     from spacy_ray_amd.vocab.vectors import load_vectors_dir
@@ -535,6 +544,10 @@ def check_static_vectors_config(cfg: Dict) -> List[str]:
             f"the n-gram rows of its distinct words (n = {vectors.minn}.."
             f"{vectors.maxn}, {vectors.hash_count} hashes per n-gram, keyed "
             f"by {vectors.key_attr})")
+    if wants_objective:
+        lines.append(
+            f"pretraining: vectors objective, loss = "
+            f"{objective.get('loss', 'cosine')}, target width {vectors.width}")
     if not wants:
         lines.append("note: [initialize] vectors is set but no model has "
                      "include_static_vectors = true (Doc.vector only)")

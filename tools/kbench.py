@@ -454,8 +454,70 @@ def bench_floret():
           f"best of 3, token hashes cached per Doc)")
 
 
+def bench_vecloss():
+    """vectors_loss (srx_vecloss.hip.h) against the composed torch path
+    (torch_ref.vectors_loss) on the same inputs: N = 150k masked tokens (15%
+    of a 1M-word step), nM = 300 (table stride 320), V = 200k, Zipf rows
+    with 5% out of vocabulary, both losses.  Both sides produce the row
+    losses, their sum and dPred, as the forward of ops.vectors_loss does."""
+    import numpy as np
+
+    from spacy_ray_amd.ops import torch_ref as ref
+
+    N, V, nM, nMp = 150_000, 200_000, 300, 320
+    rng = np.random.default_rng(0)
+    p = 1.0 / np.arange(1, V + 1)
+    rows_np = rng.choice(V, size=N, p=p / p.sum()).astype(np.int32)
+    rows_np[rng.random(N) < 0.05] = -1
+    rows = torch.from_numpy(rows_np).to(dev)
+    table = torch.zeros(V, nMp, device=dev, dtype=torch.bfloat16)
+    table[:, :nM] = torch.randn(V, nM, device=dev) * 0.5
+    pred = torch.randn(N, nM, device=dev).to(torch.bfloat16)
+    row_loss = torch.empty(N, device=dev)
+    dpred = torch.empty_like(pred)
+    scale = 1.0 / N
+    floor_bytes = N * (2 * nM * 2 + nMp * 2)
+    for loss in ("cosine", "L2"):
+        def fused():
+            hip.vectors_loss(pred, table, rows, row_loss, dpred, loss == "L2",
+                             scale)
+            return row_loss.sum() * scale
+
+        def composed():
+            rl, dp = ref.vectors_loss(pred, table, rows, loss, scale)
+            return rl.sum() * scale, dp
+
+        lf = fused()
+        lc, dc = composed()
+        diff = (dpred.float() - dc.float()).abs().max().item()
+        # alternate the two so that clock and cache state are shared
+        for _ in range(10):
+            fused()
+            composed()
+        torch.cuda.synchronize()
+        times = {"fused": [], "composed": []}
+        for _ in range(30):
+            for name, fn in (("fused", fused), ("composed", composed)):
+                a = torch.cuda.Event(enable_timing=True)
+                b = torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                times[name].append(a.elapsed_time(b))
+        print(f"vecloss {loss} (N={N}, nM={nM}, V={V}):")
+        for name, ts in times.items():
+            ts.sort()
+            med = ts[len(ts) // 2]
+            print(f"  vectors_loss {name:9s} median {med:8.3f} ms  min "
+                  f"{ts[0]:8.3f} ms  {floor_bytes / med / 1e9:8.3f} TB/s of the "
+                  f"floor bytes")
+        print(f"  loss fused {float(lf):.6f} composed {float(lc):.6f}, "
+              f"max |dPred fused - composed| = {diff:.3e}")
+
+
 ALL = {"mwe": bench_mwe, "dpre": bench_dpre, "ce": bench_ce,
-       "floret": bench_floret,
+       "floret": bench_floret, "vecloss": bench_vecloss,
        "gpustate": bench_gpustate, "attn": bench_attn,
        "static_vectors": bench_static_vectors,
        "hashembed": bench_hashembed}
