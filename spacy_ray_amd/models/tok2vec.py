@@ -67,6 +67,21 @@ class MultiHashEmbed(nn.Module):
                 vectors = (*sv.table_and_rows(batch), sv.W)
             X = ops.multi_hashembed(batch.attr_ids, self.seeds,
                                     list(self.tables), vectors)
+        mixer = self.mixer
+        if ops.mixer_layer_available(X, mixer.nO, mixer.pieces):
+            # GEMM + maxout + LayerNorm in ONE MFMA kernel.  The kernels take
+            # a dropout mask too, but a mask from ops.dropout_mask_like drops
+            # other elements than F.dropout and moved the benchmark's
+            # parameter norms by more than the documented 2^-8 run-to-run
+            # noise (docs/KERNELS.md), so dropout stays torch's, after.
+            with timing.phase("t2v/mixer_fused"):
+                Y = ops.mixer_layer(X, mixer.weight, mixer.bias,
+                                    mixer.norm.weight, mixer.norm.bias,
+                                    None, mixer.norm.eps)
+            with timing.phase("t2v/mixer_drop"):
+                if drop and self.training:
+                    Y = torch.nn.functional.dropout(Y, drop)
+            return Y
         with timing.phase("t2v/mixer_gemm"):
             Y = ops.linear_cdw(X, self.mixer.weight, self.mixer.bias)
         with timing.phase("t2v/mixer_maxout"):

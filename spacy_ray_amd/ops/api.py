@@ -1020,6 +1020,75 @@ def mwe_layer_available(X: torch.Tensor, width: int, pieces: int) -> bool:
     )
 
 
+# ------------------------------------------- fused embedding mixer (MFMA)
+class _MixerLayer(torch.autograd.Function):
+    """The MultiHashEmbed mixer as hand-written MFMA kernels
+    (srx_mixer.hip.h): Y = dropmask * LN(maxout_3(E @ W^T + bias)), E
+    [T, NS*W].  Forward: one kernel.  Backward: one kernel for stage 1
+    (mask x layernorm_bwd x maxout scatter) and dE = dPre @ W, then the dW
+    GEMM (hipBLASLt) on the saved E."""
+
+    @staticmethod
+    def forward(ctx, E, weight, bias, g, b, dropmask, eps):
+        E = E.contiguous()
+        Y, Mout, which, mu, rstd = hip_ext().mixer_fwd(
+            E, weight, bias, g, b, dropmask, eps)
+        ctx.save_for_backward(E, weight, g, which, Mout, mu, rstd,
+                              *([dropmask] if dropmask is not None else []))
+        ctx.has_mask = dropmask is not None
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        if ctx.has_mask:
+            E, weight, g, which, Mout, mu, rstd, dropmask = ctx.saved_tensors
+        else:
+            E, weight, g, which, Mout, mu, rstd = ctx.saved_tensors
+            dropmask = None
+        dY = dY.contiguous()
+        # the dg/db/dbias column sums are fixed-order (no atomics), so
+        # SRX_DETERMINISTIC needs no variant
+        dPre, dE, dg32, db32, dbias32 = hip_ext().mixer_bwd_fused(
+            dY, dropmask, Mout, g, mu, rstd, which, weight)
+        dW = mm_dw_chunked(dPre, E)
+        return (dE, dW, dbias32.to(dY.dtype), dg32.to(dY.dtype),
+                db32.to(dY.dtype), None, None)
+
+
+def mixer_layer(E, weight, bias, g, b, dropmask=None, eps: float = 1e-5):
+    return _MixerLayer.apply(E, weight, bias, g, b, dropmask, eps)
+
+
+def _mixer_composed() -> bool:
+    """SRX_MIXER=composed: the library GEMM + maxout + LayerNorm + dropout
+    chain, for comparison and as an escape hatch."""
+    mode = os.environ.get("SRX_MIXER", "")
+    if mode not in ("", "composed"):
+        raise ValueError(f"SRX_MIXER={mode!r}: expected 'composed' or unset")
+    return mode == "composed"
+
+
+def mixer_layer_available(E: torch.Tensor, width: int, pieces: int) -> bool:
+    """Where MultiHashEmbed takes the fused mixer: bf16 on the GPU, 3
+    pieces, W in {96, 128}, 4 input blocks of width W, T % 64 == 0.  The
+    kernels also cover 5 blocks (include_static_vectors; it fits in LDS and
+    is tested), but only the 4-block shape has been measured against the
+    composed chain, and the fused path is the default only where it was
+    measured not slower (docs/KERNELS.md)."""
+    composed = _mixer_composed()  # a bad SRX_MIXER raises on every path
+    return (
+        not composed
+        and E.is_cuda
+        and E.dtype == torch.bfloat16
+        and E.dim() == 2
+        and pieces == 3
+        and width in (96, 128)
+        and E.shape[1] == 4 * width
+        and E.shape[0] % 64 == 0
+        and hip_ext() is not None
+    )
+
+
 class _AddLayerNorm(torch.autograd.Function):
     """LN(X + R) with the residual add fused into the layernorm kernels'
     data passes (saves a full elementwise pass each way on the roberta

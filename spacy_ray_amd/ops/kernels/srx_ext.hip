@@ -15,6 +15,7 @@
 #include "srx_embed_parser.hip.h"
 #include "srx_softmax_reduce.hip.h"
 #include "srx_mwe.hip.h"
+#include "srx_mixer.hip.h"
 #include "srx_staticvec.hip.h"
 #include "srx_floret.hip.h"
 #include "srx_vecloss.hip.h"
@@ -1249,6 +1250,23 @@ at::Tensor mwe_bwd_dx(at::Tensor dPre, at::Tensor weight, at::Tensor starts,
   return dX;
 }
 
+// per-tile column-sum rows [n, ncols] -> one row: 64 rows per block per
+// level, added in row order (mwe_colsum_kernel)
+at::Tensor mwe_fold_partials(at::Tensor part, int ncols, hipStream_t stream) {
+  long n = part.size(0);
+  const int R = 64;
+  do {
+    long nb = (n + R - 1) / R;
+    auto out = at::empty({nb, (long)ncols}, part.options());
+    hipLaunchKernelGGL(mwe_colsum_kernel, dim3((unsigned)nb, (ncols + 63) / 64),
+                       dim3(64), 0, stream, part.data_ptr<float>(),
+                       out.data_ptr<float>(), n, R, ncols);
+    part = out;
+    n = nb;
+  } while (n > 1);
+  return part.view({(long)ncols});
+}
+
 // ------------------------------------- fused MWE backward (stage 1 + dX)
 template <int W>
 void launch_mwe_bwd_fused(const at::Tensor& dY,
@@ -1353,19 +1371,193 @@ std::vector<at::Tensor> mwe_bwd_fused(at::Tensor dY,
   else
     launch_mwe_bwd_fused<128>(dY, dropmask, Mout, g, mu, rstd, which, WT, starts,
                               ends, dPre, dX, part, T, stream);
-  // per-tile rows -> one row, 64 rows per block per level, in row order
-  const int R = 64;
-  do {
-    long nb = (n + R - 1) / R;
-    auto out = at::empty({nb, (long)ncols}, f32);
-    hipLaunchKernelGGL(mwe_colsum_kernel, dim3((unsigned)nb, (ncols + 63) / 64),
-                       dim3(64), 0, stream, part.data_ptr<float>(),
-                       out.data_ptr<float>(), n, R, ncols);
-    part = out;
-    n = nb;
-  } while (n > 1);
-  auto sums = part.view({(long)ncols});
+  auto sums = mwe_fold_partials(part, ncols, stream);
   return {dPre, dX, sums.narrow(0, 0, W), sums.narrow(0, W, W),
+          sums.narrow(0, 2L * W, 3L * W)};
+}
+
+// ------------------------------------------ fused embedding mixer (MFMA)
+// see srx_mixer.hip.h
+void mixer_check_shape(const char* name, long T, int W, int NS) {
+  TORCH_CHECK(W == 96 || W == 128, name, " supports W in {96,128}");
+  TORCH_CHECK(NS == 4 || NS == 5, name, " supports 4 or 5 input blocks of width W");
+  TORCH_CHECK(T % 64 == 0, name, " needs T % 64 == 0 (TokenBatch pads)");
+}
+
+void mixer_check_mask(const c10::optional<at::Tensor>& dropmask, long T, int W) {
+  if (!dropmask) return;
+  check_dev(*dropmask);
+  TORCH_CHECK(dropmask->scalar_type() == at::kBFloat16 && dropmask->dim() == 2 &&
+                  dropmask->size(0) == T && dropmask->size(1) == W,
+              "dropmask must be bf16 [T,W]");
+}
+
+template <int W, int NS>
+void launch_mixer_fwd(const at::Tensor& E, const at::Tensor& Wm,
+                      const at::Tensor& bias, const at::Tensor& g,
+                      const at::Tensor& b,
+                      const c10::optional<at::Tensor>& dropmask, at::Tensor& Y,
+                      at::Tensor& Mout, at::Tensor& which, at::Tensor& mu,
+                      at::Tensor& rstd, long T, double eps, hipStream_t stream) {
+  using C = MixCfg<W, NS, false>;
+  // streamed A and B chunks, reused by the epilogue tiles, + LN partials /
+  // row stats: 70 KB at W=96 -> two 6-wave workgroups per CU; 91 KB at
+  // W=128 -> one 8-wave workgroup
+  size_t lds_bytes = MixFwdLds<W, NS>::BYTES;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)mixer_fwd_kernel<W, NS>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_bytes);
+    attr_set = true;
+  }
+  dim3 grid((unsigned)((T + C::MT - 1) / C::MT));
+  hipLaunchKernelGGL((mixer_fwd_kernel<W, NS>), grid, dim3(C::NT), lds_bytes,
+                     stream, (const bf16_t*)E.data_ptr(), (const bf16_t*)Wm.data_ptr(),
+                     (const bf16_t*)bias.data_ptr(), (const bf16_t*)g.data_ptr(),
+                     (const bf16_t*)b.data_ptr(),
+                     dropmask ? (const bf16_t*)dropmask->data_ptr() : nullptr,
+                     (bf16_t*)Y.data_ptr(), (bf16_t*)Mout.data_ptr(),
+                     which.data_ptr<uint8_t>(), mu.data_ptr<float>(),
+                     rstd.data_ptr<float>(), T, (float)eps);
+}
+
+// Y = dropmask * LN(maxout_3(E @ Wm^T + bias)) in one kernel.
+// Returns {Y, Mout, which, mu, rstd}.
+std::vector<at::Tensor> mixer_fwd(at::Tensor E, at::Tensor Wm, at::Tensor bias,
+                                  at::Tensor g, at::Tensor b,
+                                  c10::optional<at::Tensor> dropmask, double eps) {
+  check_dev(E);
+  check_dev(Wm);
+  check_dev(bias);
+  check_dev(g);
+  check_dev(b);
+  TORCH_CHECK(E.scalar_type() == at::kBFloat16 &&
+                  Wm.scalar_type() == at::kBFloat16 &&
+                  bias.scalar_type() == at::kBFloat16 &&
+                  g.scalar_type() == at::kBFloat16 &&
+                  b.scalar_type() == at::kBFloat16,
+              "mixer_fwd is bf16-only");
+  TORCH_CHECK(E.dim() == 2 && Wm.dim() == 2, "mixer_fwd expects 2-d tensors");
+  TORCH_CHECK(Wm.size(0) % 3 == 0, "weight must be [3W, NS*W]");
+  long T = E.size(0);
+  int W = (int)(Wm.size(0) / 3);
+  TORCH_CHECK(W > 0 && E.size(1) % W == 0 && Wm.size(1) == E.size(1),
+              "E must be [T, NS*W] and weight [3W, NS*W]");
+  int NS = (int)(E.size(1) / W);
+  mixer_check_shape("mixer_fwd", T, W, NS);
+  TORCH_CHECK(bias.numel() == 3 * W && g.numel() == W && b.numel() == W,
+              "bias must have 3W entries, g and b W");
+  mixer_check_mask(dropmask, T, W);
+  auto Y = at::empty({T, (long)W}, E.options());
+  auto Mout = at::empty({T, (long)W}, E.options());
+  auto which = at::empty({T, (long)W}, E.options().dtype(at::kByte));
+  auto mu = at::empty({T}, E.options().dtype(at::kFloat));
+  auto rstd = at::empty({T}, E.options().dtype(at::kFloat));
+  auto stream = at::cuda::getCurrentCUDAStream();
+  if (T > 0) {
+#define SRX_MIXER_FWD(W_, NS_)                                                 \
+  if (W == W_ && NS == NS_)                                                    \
+    launch_mixer_fwd<W_, NS_>(E, Wm, bias, g, b, dropmask, Y, Mout, which, mu, \
+                              rstd, T, eps, stream);
+    SRX_MIXER_FWD(96, 4) SRX_MIXER_FWD(96, 5)
+    SRX_MIXER_FWD(128, 4) SRX_MIXER_FWD(128, 5)
+#undef SRX_MIXER_FWD
+  }
+  return {Y, Mout, which, mu, rstd};
+}
+
+template <int W, int NS>
+void launch_mixer_bwd_fused(const at::Tensor& dY,
+                            const c10::optional<at::Tensor>& dropmask,
+                            const at::Tensor& Mout, const at::Tensor& g,
+                            const at::Tensor& mu, const at::Tensor& rstd,
+                            const at::Tensor& which, const at::Tensor& WT,
+                            at::Tensor& dPre, at::Tensor& dE, at::Tensor& partials,
+                            long T, hipStream_t stream) {
+  using C = MixCfg<W, NS, true>;
+  // stage-1 image [128][3W] + double-buffered B chunks + one section's
+  // output tile: 139 KB at W=96, 152 KB at W=128 -> one workgroup per CU
+  size_t lds_bytes =
+      (size_t)(C::A_ELEMS + C::B_ELEMS + C::MT * C::OP) * sizeof(bf16_t);
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)mixer_bwd_fused_kernel<W, NS>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_bytes);
+    attr_set = true;
+  }
+  dim3 grid((unsigned)((T + C::MT - 1) / C::MT));
+  hipLaunchKernelGGL((mixer_bwd_fused_kernel<W, NS>), grid, dim3(C::NT), lds_bytes,
+                     stream, (const bf16_t*)dY.data_ptr(),
+                     dropmask ? (const bf16_t*)dropmask->data_ptr() : nullptr,
+                     (const bf16_t*)Mout.data_ptr(), (const bf16_t*)g.data_ptr(),
+                     mu.data_ptr<float>(), rstd.data_ptr<float>(),
+                     which.data_ptr<uint8_t>(), (const bf16_t*)WT.data_ptr(),
+                     (bf16_t*)dPre.data_ptr(), (bf16_t*)dE.data_ptr(),
+                     partials.data_ptr<float>(), T);
+}
+
+// Mixer backward in one kernel: stage 1 (dropmask x LayerNorm backward x
+// maxout scatter) per 128-row tile into LDS, dPre written once for the dW
+// GEMM, dE = dPre @ weight.  Fixed-order column sums (no atomics).
+// Returns {dPre, dE, dg32, db32, dbias32}.
+std::vector<at::Tensor> mixer_bwd_fused(at::Tensor dY,
+                                        c10::optional<at::Tensor> dropmask,
+                                        at::Tensor Mout, at::Tensor g,
+                                        at::Tensor mu, at::Tensor rstd,
+                                        at::Tensor which, at::Tensor weight) {
+  check_dev(dY);
+  check_dev(Mout);
+  check_dev(g);
+  check_dev(mu);
+  check_dev(rstd);
+  check_dev(which);
+  check_dev(weight);
+  TORCH_CHECK(dY.scalar_type() == at::kBFloat16 &&
+                  Mout.scalar_type() == at::kBFloat16 &&
+                  g.scalar_type() == at::kBFloat16 &&
+                  weight.scalar_type() == at::kBFloat16,
+              "mixer_bwd_fused is bf16-only");
+  TORCH_CHECK(dY.dim() == 2 && weight.dim() == 2,
+              "mixer_bwd_fused expects 2-d tensors");
+  long T = dY.size(0);
+  int W = (int)dY.size(1);
+  TORCH_CHECK(W > 0 && weight.size(0) == 3 * W && weight.size(1) % W == 0,
+              "weight must be [3W, NS*W]");
+  int NS = (int)(weight.size(1) / W);
+  mixer_check_shape("mixer_bwd_fused", T, W, NS);
+  TORCH_CHECK(Mout.dim() == 2 && Mout.size(0) == T && Mout.size(1) == W,
+              "Mout must be [T,W]");
+  TORCH_CHECK(which.scalar_type() == at::kByte && which.dim() == 2 &&
+                  which.size(0) == T && which.size(1) == W,
+              "which must be uint8 [T,W]");
+  TORCH_CHECK(mu.scalar_type() == at::kFloat && rstd.scalar_type() == at::kFloat &&
+                  mu.numel() == T && rstd.numel() == T,
+              "mu/rstd must be fp32 with T entries");
+  TORCH_CHECK(g.numel() == W, "g must have W entries");
+  mixer_check_mask(dropmask, T, W);
+  auto dPre = at::empty({T, 3L * W}, dY.options());
+  auto dE = at::empty({T, (long)NS * W}, dY.options());
+  auto f32 = dY.options().dtype(at::kFloat);
+  if (T == 0) {
+    return {dPre, dE, at::zeros({W}, f32), at::zeros({W}, f32),
+            at::zeros({3L * W}, f32)};
+  }
+  // k-contiguous B rows: section s, output column n -> WT[sW + n, :]
+  auto WT = weight.t().contiguous();
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const int ncols = 5 * W;
+  auto part = at::empty({(T + 127) / 128, (long)ncols}, f32);
+#define SRX_MIXER_BWD(W_, NS_)                                                \
+  if (W == W_ && NS == NS_)                                                   \
+    launch_mixer_bwd_fused<W_, NS_>(dY, dropmask, Mout, g, mu, rstd, which, WT, \
+                                    dPre, dE, part, T, stream);
+  SRX_MIXER_BWD(96, 4) SRX_MIXER_BWD(96, 5)
+  SRX_MIXER_BWD(128, 4) SRX_MIXER_BWD(128, 5)
+#undef SRX_MIXER_BWD
+  auto sums = mwe_fold_partials(part, ncols, stream);
+  return {dPre, dE, sums.narrow(0, 0, W), sums.narrow(0, W, W),
           sums.narrow(0, 2L * W, 3L * W)};
 }
 
@@ -1774,6 +1966,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mwe_bwd_fused", &mwe_bwd_fused, py::arg("dY"), py::arg("dropmask"),
         py::arg("Mout"), py::arg("g"), py::arg("mu"), py::arg("rstd"),
         py::arg("which"), py::arg("weight"), py::arg("starts"), py::arg("ends"));
+  m.def("mixer_fwd", &mixer_fwd, py::arg("E"), py::arg("weight"), py::arg("bias"),
+        py::arg("g"), py::arg("b"), py::arg("dropmask"), py::arg("eps"));
+  m.def("mixer_bwd_fused", &mixer_bwd_fused, py::arg("dY"), py::arg("dropmask"),
+        py::arg("Mout"), py::arg("g"), py::arg("mu"), py::arg("rstd"),
+        py::arg("which"), py::arg("weight"));
   m.def("static_vectors_fwd", &static_vectors_fwd, py::arg("table"),
         py::arg("rows"), py::arg("W"), py::arg("Y"), py::arg("col_off") = 0);
   m.def("static_vectors_bwd_dw", &static_vectors_bwd_dw, py::arg("table"),

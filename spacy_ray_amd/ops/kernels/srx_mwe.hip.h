@@ -47,10 +47,10 @@
 // gfx950; AGPR 0 and scratch 0 in all six):
 //   mwe_layer_fwd_kernel<96>   147 VGPR  LDS  77,216 B  2 workgroups (12 waves) / CU
 //   mwe_layer_fwd_kernel<128>  149 VGPR  LDS 101,920 B  1 workgroup  ( 8 waves) / CU
-//   mwe_bwd_dx_kernel<96>      112 VGPR  LDS 116,896 B  1 workgroup  ( 6 waves) / CU
+//   mwe_bwd_dx_kernel<96>      118 VGPR  LDS 116,896 B  1 workgroup  ( 6 waves) / CU
 //   mwe_bwd_dx_kernel<128>     126 VGPR  LDS 155,168 B  1 workgroup  ( 8 waves) / CU
-//   mwe_bwd_fused_kernel<96>   185 VGPR  LDS 116,896 B  1 workgroup  ( 6 waves) / CU
-//   mwe_bwd_fused_kernel<128>  163 VGPR  LDS 155,168 B  1 workgroup  ( 8 waves) / CU
+//   mwe_bwd_fused_kernel<96>   194 VGPR  LDS 116,896 B  1 workgroup  ( 6 waves) / CU
+//   mwe_bwd_fused_kernel<128>  164 VGPR  LDS 155,168 B  1 workgroup  ( 8 waves) / CU
 // Measured at T=1M, W=96 (MI355X): forward 1.32 -> 0.54 ms, dX 0.77
 // (GEMM + seq2col_bwd) -> 0.47 ms, stage 1 + dX 1.02 + 0.48 -> 0.80 ms
 // fused; see profiles/README.md.
@@ -76,6 +76,7 @@ struct MweCfg {
   static constexpr int KC = BWD ? 96 : 32;     // K chunk of the B stream
   static constexpr int BP = KC + 8;            // padded B chunk row (bf16)
   static constexpr int NBR = BWD ? W : 3 * W;  // B rows per chunk
+  static constexpr int LDB = 3 * W;            // B row stride in memory
   static constexpr int NP = BWD ? 1 : 3;       // accumulator tiles per wave / 2
   static constexpr int CPS = KA / KC;          // chunks per section
   static constexpr int NC = 3 * CPS;
@@ -99,7 +100,7 @@ __device__ __forceinline__ void mwe_b_fetch(const bf16_t* __restrict__ Bm, int c
   for (int i = 0; i < C::PF; i++) {
     const int id = i * C::NT + tid;
     const int j = id / (C::KC / 8), q = id % (C::KC / 8);
-    pf[i] = *(const srx_u32x4_t*)(Bm + (long)(rowbase + j) * (3 * C::W) +
+    pf[i] = *(const srx_u32x4_t*)(Bm + (long)(rowbase + j) * C::LDB +
                                   coloff + q * 8);
   }
 }
@@ -172,6 +173,36 @@ __device__ __forceinline__ void mwe_section_masks(
   }
 }
 
+// The MFMAs of one B chunk.  `abase` / `bbase` are this lane's fragment
+// addresses at k = 0 of the chunk; the A rows have pitch APITCH.  zr0 / zr1
+// zero the lane's two A rows (a dropped section).
+template <class C, int APITCH>
+__device__ __forceinline__ void mwe_chunk_mfma(const bf16_t* abase,
+                                               const bf16_t* bbase, bool zr0,
+                                               bool zr1,
+                                               srx_f32x16 (&acc)[C::NP][2]) {
+#pragma unroll
+  for (int ks = 0; ks < C::KC / 16; ks++) {
+    // A fragment (32x32x16 bf16): lane holds A[row (lane&31)]
+    // [k + 8*(lane>>5) + e], e=0..7 — one ds_read_b128
+    srx_bf16x8 afrag[2];
+    afrag[0] = *(const srx_bf16x8*)(abase + ks * 16);
+    afrag[1] = *(const srx_bf16x8*)(abase + 32 * APITCH + ks * 16);
+    const srx_bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (zr0) afrag[0] = zero;
+    if (zr1) afrag[1] = zero;
+#pragma unroll
+    for (int p = 0; p < C::NP; p++) {
+      srx_bf16x8 bfrag =
+          *(const srx_bf16x8*)(bbase + p * (32 * C::NW) * C::BP + ks * 16);
+#pragma unroll
+      for (int mi = 0; mi < 2; mi++)
+        acc[p][mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            afrag[mi], bfrag, acc[p][mi], 0, 0, 0);
+    }
+  }
+}
+
 // The K-chunk loop.  On entry the A image and B chunk 0 (buffer 0) are in
 // LDS and a barrier has been passed; `pf` is scratch for the B prefetch.
 // Ends with a barrier: both LDS regions are free afterwards.
@@ -200,26 +231,7 @@ __device__ __forceinline__ void mwe_chunk_loop(
     const bf16_t* abase = ldsA + arow * C::AP + kc * C::KC + 8 * (lane >> 5);
     const bf16_t* bbase = bbuf + (32 * w + (lane & 31)) * C::BP + 8 * (lane >> 5);
     const bool zr0 = (zmask[0] >> s) & 1, zr1 = (zmask[1] >> s) & 1;
-#pragma unroll
-    for (int ks = 0; ks < C::KC / 16; ks++) {
-      // A fragment (32x32x16 bf16): lane holds A[row (lane&31)]
-      // [k + 8*(lane>>5) + e], e=0..7 — one ds_read_b128
-      srx_bf16x8 afrag[2];
-      afrag[0] = *(const srx_bf16x8*)(abase + ks * 16);
-      afrag[1] = *(const srx_bf16x8*)(abase + 32 * C::AP + ks * 16);
-      const srx_bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (zr0) afrag[0] = zero;
-      if (zr1) afrag[1] = zero;
-#pragma unroll
-      for (int p = 0; p < C::NP; p++) {
-        srx_bf16x8 bfrag =
-            *(const srx_bf16x8*)(bbase + p * (32 * C::NW) * C::BP + ks * 16);
-#pragma unroll
-        for (int mi = 0; mi < 2; mi++)
-          acc[p][mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              afrag[mi], bfrag, acc[p][mi], 0, 0, 0);
-      }
-    }
+    mwe_chunk_mfma<C, C::AP>(abase, bbase, zr0, zr1, acc);
     if (c + 1 < C::NC)
       mwe_b_store<C>(ldsB + ((c + 1) & 1) * (C::NBR * C::BP), tid, pf);
     __syncthreads();
@@ -272,44 +284,28 @@ __device__ __forceinline__ float mwe_row_sums(float (&v)[16], int lane) {
 }
 
 // -------------------------------------------------------------- forward
-template <int W>
-__global__ __launch_bounds__(4 * W) void mwe_layer_fwd_kernel(
-    const bf16_t* __restrict__ X,      // [T, W]
-    const bf16_t* __restrict__ Wt,     // [3W (out, pieces-major), 3W (in)] row-major
-    const bf16_t* __restrict__ bias,   // [3W]
-    const bf16_t* __restrict__ g,      // [W]
-    const bf16_t* __restrict__ b,      // [W]
-    const uint8_t* __restrict__ is_start,
-    const uint8_t* __restrict__ is_end,
-    const bf16_t* __restrict__ dropmask,  // [T, W] 0 or 1/keep, or nullptr
-    bf16_t* __restrict__ Y,            // [T, W]
-    bf16_t* __restrict__ Mout,         // [T, W] maxout output (for bwd)
-    uint8_t* __restrict__ which,       // [T, W]
-    float* __restrict__ mu_out,        // [T]
-    float* __restrict__ rstd_out,      // [T]
-    long T, float eps) {
-  using C = MweCfg<W, false>;
-  constexpr int WP = C::AP, NW = C::NW, MT = C::MT, NT = C::NT;
-  constexpr int WHP = W + 16;  // `which` tile row stride (bytes)
-  static_assert(MT * WP * 2 + MT * WHP <= C::B_ELEMS * 2, "epilogue tiles");
-  extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
-  bf16_t* ldsA = lds;                               // X halo image, then Y
-  bf16_t* ldsB = lds + C::A_ELEMS;                  // B chunks x2
-  bf16_t* ldsM = ldsB;                              // epilogue: mask, then Mout
-  uint8_t* ldsWh = (uint8_t*)(ldsB + MT * WP);      // epilogue: which
-  float* ldsP = (float*)(ldsB + C::B_ELEMS);        // LN partials [2][NW][MT]
-  float* ldsS = ldsP + 2 * NW * MT;                 // mu, rstd [2][MT]
-
+// The forward epilogue of a 128-row tile, from the wave's accumulators
+// acc[piece][m-tile] (see the file comment).  All LDS tiles must be free on
+// entry (a barrier passed): ldsY [MT][W+8] receives Y — with RESID it holds
+// the residual on entry —, ldsM [MT][W+8] the mask and then Mout, ldsWh
+// [MT][W+16] bytes `which`; ldsP [2][NW][MT] and ldsS [2][MT] are fp32.
+template <int W, bool RESID>
+__device__ __forceinline__ void mwe_fwd_epilogue(
+    srx_f32x16 (&acc)[3][2], const bf16_t* __restrict__ bias,
+    const bf16_t* __restrict__ g, const bf16_t* __restrict__ b,
+    const bf16_t* __restrict__ dropmask, bf16_t* ldsY, bf16_t* ldsM,
+    uint8_t* ldsWh, float* ldsP, float* ldsS, bf16_t* __restrict__ Y,
+    bf16_t* __restrict__ Mout, uint8_t* __restrict__ which,
+    float* __restrict__ mu_out, float* __restrict__ rstd_out, long T, long t0,
+    float eps) {
+  constexpr int WP = W + 8, NW = W / 32, MT = 128, NT = 4 * W;
+  constexpr int WHP = W + 16;
   const int tid = threadIdx.x;
   const int lane = tid % SRX_WAVE;
   const int wave = tid / SRX_WAVE;
   const int mh = wave / NW, w = wave % NW;
-  const long t0 = (long)blockIdx.x * MT;
 
-  srx_f32x16 acc[3][2];  // [piece][m-tile]
-  mwe_tile_gemm<C>(X, Wt, is_start, is_end, T, t0, ldsA, ldsB, acc);
-
-  // ---- epilogue.  dropmask tile -> the free B region (16-byte loads)
+  // dropmask tile -> LDS (16-byte loads)
   if (dropmask) {
     for (int id = tid; id < MT * (W / 8); id += NT) {
       const int r = id / (W / 8), q = id % (W / 8);
@@ -384,7 +380,7 @@ __global__ __launch_bounds__(4 * W) void mwe_layer_fwd_kernel(
   }
   __syncthreads();
 
-  // normalise, mask, residual from the X image; results stay in LDS
+  // normalise, mask, residual from the Y tile; results stay in LDS
 #pragma unroll
   for (int mi = 0; mi < 2; mi++) {
 #pragma unroll
@@ -394,8 +390,8 @@ __global__ __launch_bounds__(4 * W) void mwe_layer_fwd_kernel(
       const float v = mx[mi][rr];
       float y = (v - mu) * rstd * gv + bv;
       if (dropmask) y *= bf2f(ldsM[r * WP + col]);
-      y += bf2f(ldsA[(r + 1) * WP + col]);  // residual
-      ldsA[(r + 1) * WP + col] = f2bf(y);
+      if (RESID) y += bf2f(ldsY[r * WP + col]);
+      ldsY[r * WP + col] = f2bf(y);
       ldsM[r * WP + col] = f2bf(v);
       ldsWh[r * WHP + col] = arg[mi][rr];
     }
@@ -407,7 +403,7 @@ __global__ __launch_bounds__(4 * W) void mwe_layer_fwd_kernel(
     const int r = id / (W / 8), q = id % (W / 8);
     if (t0 + r < T) {
       *(srx_u32x4_t*)(Y + (t0 + r) * W + q * 8) =
-          *(const srx_u32x4_t*)(ldsA + (r + 1) * WP + q * 8);
+          *(const srx_u32x4_t*)(ldsY + r * WP + q * 8);
       *(srx_u32x4_t*)(Mout + (t0 + r) * W + q * 8) =
           *(const srx_u32x4_t*)(ldsM + r * WP + q * 8);
     }
@@ -418,6 +414,44 @@ __global__ __launch_bounds__(4 * W) void mwe_layer_fwd_kernel(
       *(srx_u32x4_t*)(which + (t0 + r) * W + q * 16) =
           *(const srx_u32x4_t*)(ldsWh + r * WHP + q * 16);
   }
+}
+
+template <int W>
+__global__ __launch_bounds__(4 * W) void mwe_layer_fwd_kernel(
+    const bf16_t* __restrict__ X,      // [T, W]
+    const bf16_t* __restrict__ Wt,     // [3W (out, pieces-major), 3W (in)] row-major
+    const bf16_t* __restrict__ bias,   // [3W]
+    const bf16_t* __restrict__ g,      // [W]
+    const bf16_t* __restrict__ b,      // [W]
+    const uint8_t* __restrict__ is_start,
+    const uint8_t* __restrict__ is_end,
+    const bf16_t* __restrict__ dropmask,  // [T, W] 0 or 1/keep, or nullptr
+    bf16_t* __restrict__ Y,            // [T, W]
+    bf16_t* __restrict__ Mout,         // [T, W] maxout output (for bwd)
+    uint8_t* __restrict__ which,       // [T, W]
+    float* __restrict__ mu_out,        // [T]
+    float* __restrict__ rstd_out,      // [T]
+    long T, float eps) {
+  using C = MweCfg<W, false>;
+  constexpr int WP = C::AP, NW = C::NW, MT = C::MT;
+  constexpr int WHP = W + 16;  // `which` tile row stride (bytes)
+  static_assert(MT * WP * 2 + MT * WHP <= C::B_ELEMS * 2, "epilogue tiles");
+  extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
+  bf16_t* ldsA = lds;                               // X halo image, then Y
+  bf16_t* ldsB = lds + C::A_ELEMS;                  // B chunks x2
+  bf16_t* ldsM = ldsB;                              // epilogue: mask, then Mout
+  uint8_t* ldsWh = (uint8_t*)(ldsB + MT * WP);      // epilogue: which
+  float* ldsP = (float*)(ldsB + C::B_ELEMS);        // LN partials [2][NW][MT]
+  float* ldsS = ldsP + 2 * NW * MT;                 // mu, rstd [2][MT]
+  const long t0 = (long)blockIdx.x * MT;
+
+  srx_f32x16 acc[3][2];  // [piece][m-tile]
+  mwe_tile_gemm<C>(X, Wt, is_start, is_end, T, t0, ldsA, ldsB, acc);
+
+  // Y tile = the X image's own rows: the residual is read from it
+  mwe_fwd_epilogue<W, true>(acc, bias, g, b, dropmask, ldsA + WP, ldsM, ldsWh,
+                            ldsP, ldsS, Y, Mout, which, mu_out, rstd_out, T, t0,
+                            eps);
 }
 
 // ---------------------------------------------------------- backward dX
@@ -565,47 +599,24 @@ __global__ void mwe_bwd_stage1_kernel(
 // waves through the free B region, and leave as one fp32 row [5W] =
 // dg | db | dbias per workgroup.  mwe_colsum_kernel adds those rows in a
 // fixed order: no atomics, bit-reproducible in every mode.
-template <int W>
-__global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
-    const bf16_t* __restrict__ dY,        // [T, W]
-    const bf16_t* __restrict__ dropmask,  // [T, W] or nullptr
-    const bf16_t* __restrict__ Mout,      // [T, W]
-    const bf16_t* __restrict__ g,         // [W]
-    const float* __restrict__ mu,         // [T]
-    const float* __restrict__ rstd,       // [T]
-    const uint8_t* __restrict__ which,    // [T, W]
-    const bf16_t* __restrict__ WT,        // [3W, 3W] = weight^T, row-major
-    const uint8_t* __restrict__ is_start,
-    const uint8_t* __restrict__ is_end,
-    bf16_t* __restrict__ dPre,            // [T, 3W]
-    bf16_t* __restrict__ dX,              // [T, W]
-    float* __restrict__ partials,         // [gridDim.x, 5W]
-    long T) {
-  using C = MweCfg<W, true>;
-  constexpr int NW = C::NW, MT = C::MT, NT = C::NT, AP = C::AP;
+
+// The stage-1 prologue (shared with the mixer backward, srx_mixer.hip.h):
+// image row i = stage 1 of row t0 - HALO + i (zero outside [0, T)), rows of
+// pitch AP, for i < 128 + 2 HALO.  The column sums of the tile's own rows
+// are returned in dg_out / db_out / dbias_out for mwe_colsums_park.  (They
+// accumulate in locals and are copied out at the end: accumulating through
+// the references keeps the arrays out of registers — 256 VGPRs and scratch.)
+template <int W, int NT, int AP, int HALO>
+__device__ __forceinline__ void mwe_stage1_tile(
+    const bf16_t* __restrict__ dY, const bf16_t* __restrict__ dropmask,
+    const bf16_t* __restrict__ Mout, const bf16_t* __restrict__ g,
+    const float* __restrict__ mu, const float* __restrict__ rstd,
+    const uint8_t* __restrict__ which, long T, long t0, int tid, bf16_t* ldsA,
+    float (&dg_out)[8], float (&db_out)[8], float (&dbias_out)[3][8]) {
+  constexpr int MT = 128, A_ROWS = MT + 2 * HALO;
   constexpr int Q = W / 8;                        // 16-byte groups per row
   constexpr int RG = NT / 16;                     // rows per prologue pass
-  constexpr int NPASS = (C::A_ROWS + RG - 1) / RG;
-  constexpr int NWAVE = NT / SRX_WAVE;
-  constexpr int OP = W + 4;  // fp32 output tile row stride
-  static_assert(MT * OP * 4 <= C::A_ELEMS * 2, "output tile");
-  static_assert(NWAVE * 5 * W * 4 <= C::B_ELEMS * 2, "column-sum partials");
-  extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
-  bf16_t* ldsA = lds;
-  bf16_t* ldsB = lds + C::A_ELEMS;
-  float* ldsO = (float*)lds;   // epilogue: fp32 [MT][OP] over the A image
-  float* ldsC = (float*)ldsB;  // epilogue: column sums [NWAVE][5W] over B
-
-  const int tid = threadIdx.x;
-  const int lane = tid % SRX_WAVE;
-  const int wave = tid / SRX_WAVE;
-  const int mh = wave / NW, w = wave % NW;
-  const long t0 = (long)blockIdx.x * MT;
-
-  srx_u32x4_t pf[C::PF];
-  mwe_b_fetch<C>(WT, 0, tid, pf);
-
-  // ---- stage-1 prologue
+  constexpr int NPASS = (A_ROWS + RG - 1) / RG;
   const int q = tid & 15, rg = tid >> 4;
   const bool qv = q < Q;
   float gv[8];
@@ -619,14 +630,14 @@ __global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
 #pragma unroll
   for (int ps = 0; ps < NPASS; ps++) {
     const int i = ps * RG + rg;
-    const long t = t0 - 1 + i;
+    const long t = t0 - HALO + i;
     rdy[ps] = srx_u32x4_t{0u, 0u, 0u, 0u};
     rmk[ps] = srx_u32x4_t{0u, 0u, 0u, 0u};
     rmo[ps] = srx_u32x4_t{0u, 0u, 0u, 0u};
     rwh[ps] = make_uint2(0u, 0u);
     rmu[ps] = 0.f;
     rrs[ps] = 0.f;
-    if (qv && i < C::A_ROWS && t >= 0 && t < T) {
+    if (qv && i < A_ROWS && t >= 0 && t < T) {
       rdy[ps] = *(const srx_u32x4_t*)(dY + t * W + q * 8);
       if (dropmask) rmk[ps] = *(const srx_u32x4_t*)(dropmask + t * W + q * 8);
       rmo[ps] = *(const srx_u32x4_t*)(Mout + t * W + q * 8);
@@ -647,9 +658,9 @@ __global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
 #pragma unroll
   for (int ps = 0; ps < NPASS; ps++) {
     const int i = ps * RG + rg;
-    const long t = t0 - 1 + i;
-    const bool live = qv && i < C::A_ROWS && t >= 0 && t < T;
-    const bool own = live && i >= 1 && i <= MT;
+    const long t = t0 - HALO + i;
+    const bool live = qv && i < A_ROWS && t >= 0 && t < T;
+    const bool own = live && i >= HALO && i < MT + HALO;
     const float m = rmu[ps], r = rrs[ps];
     float d[8], xh[8], dxh[8];
     float s1 = 0.f, s2 = 0.f;
@@ -677,14 +688,14 @@ __global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
       wh[j] = ((j < 4 ? rwh[ps].x : rwh[ps].y) >> (8 * (j & 3))) & 0xffu;
       hb[j] = live ? (uint32_t)f2bf(dM) : 0u;
       if (own) {
-        dg_loc[j] += d[j] * xh[j];
+        dg_loc[j] = fmaf(d[j], xh[j], dg_loc[j]);
         db_loc[j] += d[j];
 #pragma unroll
         for (int p = 0; p < 3; p++) dbias_loc[p][j] += (wh[j] == (uint32_t)p) ? dM : 0.f;
       }
     }
     // expanded row: dM at piece `which`, exact zero in the other two
-    if (qv && i < C::A_ROWS) {
+    if (qv && i < A_ROWS) {
 #pragma unroll
       for (int p = 0; p < 3; p++) {
         srx_u32x4_t o;
@@ -696,24 +707,25 @@ __global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
       }
     }
   }
-
-  int zmask[2];
-  mwe_section_masks<C>(is_start, is_end, T, t0, mh, lane, zmask);
-  mwe_b_store<C>(ldsB, tid, pf);
-  __syncthreads();
-
-  // ---- dPre out: the tile's own rows, before the epilogue reuses the image
-  for (int id = tid; id < MT * (3 * Q); id += NT) {
-    const int r = id / (3 * Q), c = id % (3 * Q);
-    if (t0 + r < T)
-      *(srx_u32x4_t*)(dPre + (t0 + r) * (3 * W) + c * 8) =
-          *(const srx_u32x4_t*)(ldsA + (r + 1) * AP + c * 8);
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    dg_out[j] = dg_loc[j];
+    db_out[j] = db_loc[j];
+#pragma unroll
+    for (int p = 0; p < 3; p++) dbias_out[p][j] = dbias_loc[p][j];
   }
+}
 
-  srx_f32x16 acc[1][2];
-  mwe_chunk_loop<C>(WT, ldsA, ldsB, zmask, pf, acc);
-
-  // ---- column sums: fold the wave's 4 row groups, park per wave in LDS
+// Column sums of mwe_stage1_tile: fold the wave's 4 row groups and park one
+// row [5W] = dg | db | dbias per wave in ldsC ...
+template <int W>
+__device__ __forceinline__ void mwe_colsums_park(float (&dg_loc)[8],
+                                                 float (&db_loc)[8],
+                                                 float (&dbias_loc)[3][8],
+                                                 float* ldsC, int tid) {
+  const int lane = tid % SRX_WAVE, wave = tid / SRX_WAVE;
+  const int q = tid & 15;
+  const bool qv = q < W / 8;
 #pragma unroll
   for (int j = 0; j < 8; j++) {
 #pragma unroll
@@ -737,6 +749,80 @@ __global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
       ElemV<float, 4>::st(row + (2 + p) * W + 4, dbias_loc[p] + 4);
     }
   }
+}
+
+// ... and, after a barrier, add the waves' rows in order into the tile's row
+template <int W, int NT>
+__device__ __forceinline__ void mwe_colsums_out(const float* ldsC,
+                                                float* __restrict__ out, int tid) {
+  for (int c = tid; c < 5 * W; c += NT) {
+    float s = 0.f;
+#pragma unroll
+    for (int wv = 0; wv < NT / SRX_WAVE; wv++) s += ldsC[wv * (5 * W) + c];
+    out[c] = s;
+  }
+}
+
+template <int W>
+__global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
+    const bf16_t* __restrict__ dY,        // [T, W]
+    const bf16_t* __restrict__ dropmask,  // [T, W] or nullptr
+    const bf16_t* __restrict__ Mout,      // [T, W]
+    const bf16_t* __restrict__ g,         // [W]
+    const float* __restrict__ mu,         // [T]
+    const float* __restrict__ rstd,       // [T]
+    const uint8_t* __restrict__ which,    // [T, W]
+    const bf16_t* __restrict__ WT,        // [3W, 3W] = weight^T, row-major
+    const uint8_t* __restrict__ is_start,
+    const uint8_t* __restrict__ is_end,
+    bf16_t* __restrict__ dPre,            // [T, 3W]
+    bf16_t* __restrict__ dX,              // [T, W]
+    float* __restrict__ partials,         // [gridDim.x, 5W]
+    long T) {
+  using C = MweCfg<W, true>;
+  constexpr int NW = C::NW, MT = C::MT, NT = C::NT, AP = C::AP;
+  constexpr int Q = W / 8;                        // 16-byte groups per row
+  constexpr int NWAVE = NT / SRX_WAVE;
+  constexpr int OP = W + 4;  // fp32 output tile row stride
+  static_assert(MT * OP * 4 <= C::A_ELEMS * 2, "output tile");
+  static_assert(NWAVE * 5 * W * 4 <= C::B_ELEMS * 2, "column-sum partials");
+  extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
+  bf16_t* ldsA = lds;
+  bf16_t* ldsB = lds + C::A_ELEMS;
+  float* ldsO = (float*)lds;   // epilogue: fp32 [MT][OP] over the A image
+  float* ldsC = (float*)ldsB;  // epilogue: column sums [NWAVE][5W] over B
+
+  const int tid = threadIdx.x;
+  const int lane = tid % SRX_WAVE;
+  const int wave = tid / SRX_WAVE;
+  const int mh = wave / NW, w = wave % NW;
+  const long t0 = (long)blockIdx.x * MT;
+
+  srx_u32x4_t pf[C::PF];
+  mwe_b_fetch<C>(WT, 0, tid, pf);
+
+  float dg_loc[8], db_loc[8], dbias_loc[3][8];
+  mwe_stage1_tile<W, NT, AP, 1>(dY, dropmask, Mout, g, mu, rstd, which, T, t0,
+                                tid, ldsA, dg_loc, db_loc, dbias_loc);
+
+  int zmask[2];
+  mwe_section_masks<C>(is_start, is_end, T, t0, mh, lane, zmask);
+  mwe_b_store<C>(ldsB, tid, pf);
+  __syncthreads();
+
+  // ---- dPre out: the tile's own rows, before the epilogue reuses the image
+  for (int id = tid; id < MT * (3 * Q); id += NT) {
+    const int r = id / (3 * Q), c = id % (3 * Q);
+    if (t0 + r < T)
+      *(srx_u32x4_t*)(dPre + (t0 + r) * (3 * W) + c * 8) =
+          *(const srx_u32x4_t*)(ldsA + (r + 1) * AP + c * 8);
+  }
+
+  srx_f32x16 acc[1][2];
+  mwe_chunk_loop<C>(WT, ldsA, ldsB, zmask, pf, acc);
+
+  // ---- column sums, per wave, into the free B region
+  mwe_colsums_park<W>(dg_loc, db_loc, dbias_loc, ldsC, tid);
 
   // ---- dX epilogue (as mwe_bwd_dx_kernel)
   const int col = 32 * w + (lane & 31);
@@ -760,12 +846,7 @@ __global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
       ElemV<bf16_t, 8>::st(dX + (t0 + r) * W + qq * 8, v);
     }
   }
-  for (int c = tid; c < 5 * W; c += NT) {
-    float s = 0.f;
-#pragma unroll
-    for (int wv = 0; wv < NWAVE; wv++) s += ldsC[wv * (5 * W) + c];
-    partials[(long)blockIdx.x * (5 * W) + c] = s;
-  }
+  mwe_colsums_out<W, NT>(ldsC, partials + (long)blockIdx.x * (5 * W), tid);
 }
 
 // out[b, c] = sum over rows [b R, min((b+1) R, n)) of in[:, c], added in row

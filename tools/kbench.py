@@ -516,7 +516,69 @@ def bench_vecloss():
               f"max |dPred fused - composed| = {diff:.3e}")
 
 
-ALL = {"mwe": bench_mwe, "dpre": bench_dpre, "ce": bench_ce,
+def bench_mixer():
+    """Fused mixer (mixer_fwd / mixer_bwd_fused + dW) against the composed
+    chain (linear_cdw -> maxout -> layernorm -> * mask and its autograd
+    backward), forward and backward, T = 1M, W = 96, NS = 4, with mask.  The
+    two paths alternate in one loop; median of 30 event-timed calls after 10
+    warm-ups.  Bytes: the fused forward reads E and the mask and writes Y,
+    Mout and which; the fused backward kernel reads dY, the mask, Mout and
+    which and writes dPre and dE (its dW GEMM is timed with it, as the
+    composed backward's is)."""
+    from spacy_ray_amd.ops import api as ops
+
+    T, W, NS = 1 << 20, 96, 4
+    bf = torch.bfloat16
+    E = (torch.randn(T, NS * W, device=dev) * 0.5).to(bf).requires_grad_(True)
+    Wm = (torch.randn(3 * W, NS * W, device=dev) / (NS * W) ** 0.5).to(bf) \
+        .requires_grad_(True)
+    bias = torch.zeros(3 * W, device=dev, dtype=bf, requires_grad=True)
+    g = torch.ones(W, device=dev, dtype=bf, requires_grad=True)
+    b = torch.zeros(W, device=dev, dtype=bf, requires_grad=True)
+    mask = ops.dropout_mask_like(torch.empty(T, W, device=dev, dtype=bf), 0.1)
+    dY = torch.randn(T, W, device=dev).to(bf)
+    leaves = (E, Wm, bias, g, b)
+
+    def fused():
+        return ops.mixer_layer(E, Wm, bias, g, b, mask, 1e-5)
+
+    def composed():
+        Y = ops.linear_cdw(E, Wm, bias)
+        Y = ops.maxout(Y.view(T, 3, W))
+        return ops.layernorm(Y, g, b, 1e-5) * mask
+
+    def timed(fn):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    ts = {(n, d): [] for n in ("fused", "composed") for d in ("fwd", "bwd")}
+    for it in range(40):
+        for name, fn in (("fused", fused), ("composed", composed)):
+            t_f, Y = timed(fn)
+            t_b, _ = timed(lambda: torch.autograd.grad(Y, leaves, dY))
+            if it >= 10:
+                ts[name, "fwd"].append(t_f)
+                ts[name, "bwd"].append(t_b)
+    fwd_bytes = T * (NS * W * 2 + W * 2 + 2 * W * 2 + W)
+    bwd_bytes = T * (2 * W * 2 + W * 2 + W + 3 * W * 2 + NS * W * 2)
+    for d, nbytes in (("fwd", fwd_bytes), ("bwd", bwd_bytes)):
+        for name in ("fused", "composed"):
+            v = sorted(ts[name, d])
+            med = v[len(v) // 2]
+            extra = ""
+            if name == "fused":
+                extra = (f"  {nbytes / 1e9:.2f} GB -> {nbytes / med / 1e9:.2f} "
+                         f"TB/s" + (" (incl. dW GEMM time)" if d == "bwd" else ""))
+            print(f"  mixer {d} {name:9s} median {med:7.3f} ms  min {v[0]:7.3f} "
+                  f"max {v[-1]:7.3f}{extra}")
+
+
+ALL = {"mwe": bench_mwe, "dpre": bench_dpre, "ce": bench_ce, "mixer": bench_mixer,
        "floret": bench_floret, "vecloss": bench_vecloss,
        "gpustate": bench_gpustate, "attn": bench_attn,
        "static_vectors": bench_static_vectors,
