@@ -970,7 +970,10 @@ class _MWELayer(torch.autograd.Function):
     Y = X + LN(maxout_3(seq2col(X) @ W^T + bias)).  Forward is the fused
     gfx950 kernel (srx_mwe.hip.h); backward: one fused kernel for stage 1
     (mask x layernorm_bwd x maxout scatter) and dX (dPre @ W, seq2col_bwd
-    and the residual) -> dW GEMM (hipBLASLt) with seq2col recomputed."""
+    and the residual), then dW.  At W = 96 the fused kernel stores the compact
+    dM [T, W] and mwe_bwd_dw (srx_mwe_dw.hip.h) computes dW from dM, `which`
+    and X; otherwise (W = 128, SRX_MWE_DW=composed) dPre [T, 3W] is written
+    and dW is the hipBLASLt GEMM on the recomputed seq2col."""
 
     @staticmethod
     def forward(ctx, X, weight, bias, g, b, starts, ends, dropmask, eps):
@@ -993,16 +996,40 @@ class _MWELayer(torch.autograd.Function):
         dY = dY.contiguous()
         # ONE kernel: stage 1 (dropout mask x LN backward x maxout scatter)
         # per 128-row tile straight into the LDS image of the dX GEMM
-        # (dX = dY + seq2col_bwd(dPre @ weight)); dPre is written once for
-        # the dW GEMM and never read back.  The dg/db/dbias column sums are
-        # fixed-order (no atomics), so SRX_DETERMINISTIC needs no variant.
-        dPre, dX, dg32, db32, dbias32 = hip.mwe_bwd_fused(
-            dY, dropmask, Mout, g, mu, rstd, which, weight, starts, ends)
-        # GEMM backwards (pre = X3 @ W^T)
-        X3 = hip.seq2col_fwd(X, starts, ends)
-        dW = mm_dw_chunked(dPre, X3)
+        # (dX = dY + seq2col_bwd(dPre @ weight)).  The dg/db/dbias column
+        # sums are fixed-order (no atomics), so SRX_DETERMINISTIC needs no
+        # variant; neither does mwe_bwd_dw.
+        if mwe_dw_available(X.shape[1]):
+            dM, dX, dg32, db32, dbias32 = hip.mwe_bwd_fused(
+                dY, dropmask, Mout, g, mu, rstd, which, weight, starts, ends,
+                compact=True)
+            dW = hip.mwe_bwd_dw(dM, which, X.contiguous(), starts, ends)
+        else:
+            # dPre is written once for the dW GEMM and never read back
+            dPre, dX, dg32, db32, dbias32 = hip.mwe_bwd_fused(
+                dY, dropmask, Mout, g, mu, rstd, which, weight, starts, ends)
+            # GEMM backwards (pre = X3 @ W^T)
+            X3 = hip.seq2col_fwd(X, starts, ends)
+            dW = mm_dw_chunked(dPre, X3)
         return (dX, dW, dbias32.to(dY.dtype), dg32.to(dY.dtype),
                 db32.to(dY.dtype), None, None, None, None)
+
+
+def _mwe_dw_composed() -> bool:
+    """SRX_MWE_DW=composed: dPre [T, 3W] + seq2col + the chunked library
+    GEMM for the MWE weight gradient, for comparison and as an escape hatch."""
+    mode = os.environ.get("SRX_MWE_DW", "")
+    if mode not in ("", "composed"):
+        raise ValueError(f"SRX_MWE_DW={mode!r}: expected 'composed' or unset")
+    return mode == "composed"
+
+
+def mwe_dw_available(width: int) -> bool:
+    """Where the MWE backward takes mwe_bwd_dw: W = 96 (the 288 x 288 fp32
+    accumulator fits one workgroup's registers; 384 x 384 at W = 128 does
+    not, docs/KERNELS.md)."""
+    composed = _mwe_dw_composed()  # a bad SRX_MWE_DW raises on every path
+    return (not composed) and width == 96
 
 
 def mwe_layer(X, weight, bias, g, b, starts, ends, dropmask=None, eps: float = 1e-5):

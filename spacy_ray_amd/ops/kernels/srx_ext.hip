@@ -16,6 +16,7 @@
 #include "srx_softmax_reduce.hip.h"
 #include "srx_mwe.hip.h"
 #include "srx_mixer.hip.h"
+#include "srx_mwe_dw.hip.h"
 #include "srx_staticvec.hip.h"
 #include "srx_floret.hip.h"
 #include "srx_vecloss.hip.h"
@@ -1268,7 +1269,7 @@ at::Tensor mwe_fold_partials(at::Tensor part, int ncols, hipStream_t stream) {
 }
 
 // ------------------------------------- fused MWE backward (stage 1 + dX)
-template <int W>
+template <int W, bool COMPACT>
 void launch_mwe_bwd_fused(const at::Tensor& dY,
                           const c10::optional<at::Tensor>& dropmask,
                           const at::Tensor& Mout, const at::Tensor& g,
@@ -1283,13 +1284,13 @@ void launch_mwe_bwd_fused(const at::Tensor& dY,
   size_t lds_bytes = (size_t)(C::A_ELEMS + C::B_ELEMS) * sizeof(bf16_t);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)mwe_bwd_fused_kernel<W>,
+    (void)hipFuncSetAttribute((const void*)mwe_bwd_fused_kernel<W, COMPACT>,
                               hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds_bytes);
     attr_set = true;
   }
   dim3 grid((unsigned)((T + C::MT - 1) / C::MT));
-  hipLaunchKernelGGL((mwe_bwd_fused_kernel<W>), grid, dim3(C::NT), lds_bytes,
+  hipLaunchKernelGGL((mwe_bwd_fused_kernel<W, COMPACT>), grid, dim3(C::NT), lds_bytes,
                      stream, (const bf16_t*)dY.data_ptr(),
                      dropmask ? (const bf16_t*)dropmask->data_ptr() : nullptr,
                      (const bf16_t*)Mout.data_ptr(), (const bf16_t*)g.data_ptr(),
@@ -1305,12 +1306,16 @@ void launch_mwe_bwd_fused(const at::Tensor& dY,
 // (for the dW GEMM), never read back.  The column sums leave as one fp32
 // row per tile and are added in a fixed order (no atomics): the same
 // kernel serves SRX_DETERMINISTIC.  Returns {dPre, dX, dg32, db32, dbias32}.
+// compact: the first output is dM [T, W] (dPre[t, which[t,c] W + c], the
+// input of mwe_bwd_dw) instead of the expanded dPre [T, 3W]; the others are
+// bit-identical.
 std::vector<at::Tensor> mwe_bwd_fused(at::Tensor dY,
                                       c10::optional<at::Tensor> dropmask,
                                       at::Tensor Mout, at::Tensor g,
                                       at::Tensor mu, at::Tensor rstd,
                                       at::Tensor which, at::Tensor weight,
-                                      at::Tensor starts, at::Tensor ends) {
+                                      at::Tensor starts, at::Tensor ends,
+                                      bool compact) {
   check_dev(dY);
   check_dev(Mout);
   check_dev(g);
@@ -1352,7 +1357,7 @@ std::vector<at::Tensor> mwe_bwd_fused(at::Tensor dY,
                     dropmask->size(0) == T && dropmask->size(1) == W,
                 "dropmask must be bf16 [T,W]");
   }
-  auto dPre = at::empty({T, 3L * W}, dY.options());
+  auto dPre = at::empty({T, (compact ? 1L : 3L) * W}, dY.options());
   auto dX = at::empty_like(dY);
   auto f32 = dY.options().dtype(at::kFloat);
   if (T == 0) {
@@ -1365,15 +1370,84 @@ std::vector<at::Tensor> mwe_bwd_fused(at::Tensor dY,
   const int ncols = 5 * W;
   long n = (T + 127) / 128;
   auto part = at::empty({n, (long)ncols}, f32);
-  if (W == 96)
-    launch_mwe_bwd_fused<96>(dY, dropmask, Mout, g, mu, rstd, which, WT, starts,
-                             ends, dPre, dX, part, T, stream);
+  if (W == 96 && compact)
+    launch_mwe_bwd_fused<96, true>(dY, dropmask, Mout, g, mu, rstd, which, WT,
+                                   starts, ends, dPre, dX, part, T, stream);
+  else if (W == 96)
+    launch_mwe_bwd_fused<96, false>(dY, dropmask, Mout, g, mu, rstd, which, WT,
+                                    starts, ends, dPre, dX, part, T, stream);
+  else if (compact)
+    launch_mwe_bwd_fused<128, true>(dY, dropmask, Mout, g, mu, rstd, which, WT,
+                                    starts, ends, dPre, dX, part, T, stream);
   else
-    launch_mwe_bwd_fused<128>(dY, dropmask, Mout, g, mu, rstd, which, WT, starts,
-                              ends, dPre, dX, part, T, stream);
+    launch_mwe_bwd_fused<128, false>(dY, dropmask, Mout, g, mu, rstd, which, WT,
+                                     starts, ends, dPre, dX, part, T, stream);
   auto sums = mwe_fold_partials(part, ncols, stream);
   return {dPre, dX, sums.narrow(0, 0, W), sums.narrow(0, W, W),
           sums.narrow(0, 2L * W, 3L * W)};
+}
+
+// ------------------------------------------------ MWE dW (srx_mwe_dw.hip.h)
+// dW [3W, 3W] bf16 from dM (compact mwe_bwd_fused), which, X and the doc
+// boundaries: persistent MFMA kernel + fixed-order reduction of the
+// per-workgroup fp32 partials.  max_groups caps the number of workgroups
+// (default: one per CU), so tests can force several tiles per workgroup.
+at::Tensor mwe_bwd_dw(at::Tensor dM, at::Tensor which, at::Tensor X,
+                      at::Tensor starts, at::Tensor ends, int64_t max_groups) {
+  check_dev(dM);
+  check_dev(which);
+  check_dev(X);
+  check_dev(starts);
+  check_dev(ends);
+  TORCH_CHECK(which.device() == dM.device() && X.device() == dM.device() &&
+                  starts.device() == dM.device() && ends.device() == dM.device(),
+              "mwe_bwd_dw: all tensors must be on one device");
+  TORCH_CHECK(dM.scalar_type() == at::kBFloat16 && X.scalar_type() == at::kBFloat16,
+              "mwe_bwd_dw is bf16-only");
+  TORCH_CHECK(dM.dim() == 2 && X.dim() == 2 && which.dim() == 2,
+              "mwe_bwd_dw expects 2-d tensors");
+  TORCH_CHECK(dM.is_contiguous() && X.is_contiguous() && which.is_contiguous() &&
+                  starts.is_contiguous() && ends.is_contiguous(),
+              "mwe_bwd_dw expects contiguous tensors");
+  const long T = dM.size(0);
+  const int W = (int)dM.size(1);
+  TORCH_CHECK(W == 96, "mwe_bwd_dw supports W = 96");
+  TORCH_CHECK(T % 64 == 0, "mwe_bwd_dw needs T % 64 == 0 (TokenBatch pads)");
+  TORCH_CHECK(X.size(0) == T && X.size(1) == W, "X must be [T,W]");
+  TORCH_CHECK(which.scalar_type() == at::kByte && which.size(0) == T &&
+                  which.size(1) == W,
+              "which must be uint8 [T,W]");
+  TORCH_CHECK(starts.scalar_type() == at::kByte && ends.scalar_type() == at::kByte,
+              "starts/ends must be uint8");
+  TORCH_CHECK(starts.dim() == 1 && ends.dim() == 1 && starts.numel() == T &&
+                  ends.numel() == T,
+              "starts/ends must have T entries");
+  if (T == 0) return at::zeros({3L * W, 3L * W}, dM.options());
+  using C = MweDwCfg<96>;
+  const long ntiles = (T + C::MT - 1) / C::MT;
+  long G = std::min<long>(ntiles,
+                          at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
+  if (max_groups > 0) G = std::min<long>(G, max_groups);
+  const int n = 9 * W * W;
+  auto ws = at::empty({G, 3L * W, 3L * W}, dM.options().dtype(at::kFloat));
+  auto dW = at::empty({3L * W, 3L * W}, dM.options());
+  auto stream = at::cuda::getCurrentCUDAStream();
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)mwe_bwd_dw_kernel<96>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)C::LDS_BYTES);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((mwe_bwd_dw_kernel<96>), dim3((unsigned)G), dim3(C::NT),
+                     (size_t)C::LDS_BYTES, stream, (const bf16_t*)dM.data_ptr(),
+                     which.data_ptr<uint8_t>(), (const bf16_t*)X.data_ptr(),
+                     starts.data_ptr<uint8_t>(), ends.data_ptr<uint8_t>(),
+                     ws.data_ptr<float>(), T, (int)ntiles);
+  hipLaunchKernelGGL(mwe_dw_reduce_kernel, dim3((n + kBlock - 1) / kBlock),
+                     dim3(kBlock), 0, stream, ws.data_ptr<float>(),
+                     (bf16_t*)dW.data_ptr(), (int)G, n);
+  return dW;
 }
 
 // ------------------------------------------ fused embedding mixer (MFMA)
@@ -1965,7 +2039,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("starts"), py::arg("ends"), py::arg("dY"));
   m.def("mwe_bwd_fused", &mwe_bwd_fused, py::arg("dY"), py::arg("dropmask"),
         py::arg("Mout"), py::arg("g"), py::arg("mu"), py::arg("rstd"),
-        py::arg("which"), py::arg("weight"), py::arg("starts"), py::arg("ends"));
+        py::arg("which"), py::arg("weight"), py::arg("starts"), py::arg("ends"),
+        py::arg("compact") = false);
+  m.def("mwe_bwd_dw", &mwe_bwd_dw, py::arg("dM"), py::arg("which"), py::arg("X"),
+        py::arg("starts"), py::arg("ends"), py::arg("max_groups") = 0);
   m.def("mixer_fwd", &mixer_fwd, py::arg("E"), py::arg("weight"), py::arg("bias"),
         py::arg("g"), py::arg("b"), py::arg("dropmask"), py::arg("eps"));
   m.def("mixer_bwd_fused", &mixer_bwd_fused, py::arg("dY"), py::arg("dropmask"),

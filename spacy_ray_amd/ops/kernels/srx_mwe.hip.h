@@ -44,12 +44,13 @@
 // (tests, tools/kbench.py).
 //
 // Compiler resource report (hipcc -Rpass-analysis=kernel-resource-usage,
-// gfx950; AGPR 0 and scratch 0 in all six):
+// gfx950; AGPR 0 and scratch 0 in all of them):
 //   mwe_layer_fwd_kernel<96>   147 VGPR  LDS  77,216 B  2 workgroups (12 waves) / CU
 //   mwe_layer_fwd_kernel<128>  149 VGPR  LDS 101,920 B  1 workgroup  ( 8 waves) / CU
 //   mwe_bwd_dx_kernel<96>      118 VGPR  LDS 116,896 B  1 workgroup  ( 6 waves) / CU
 //   mwe_bwd_dx_kernel<128>     126 VGPR  LDS 155,168 B  1 workgroup  ( 8 waves) / CU
-//   mwe_bwd_fused_kernel<96>   194 VGPR  LDS 116,896 B  1 workgroup  ( 6 waves) / CU
+//   mwe_bwd_fused_kernel<96>   189 VGPR  LDS 116,896 B  1 workgroup  ( 6 waves) / CU
+//   mwe_bwd_fused_kernel<96, COMPACT>  204 VGPR, same LDS and occupancy
 //   mwe_bwd_fused_kernel<128>  164 VGPR  LDS 155,168 B  1 workgroup  ( 8 waves) / CU
 // Measured at T=1M, W=96 (MI355X): forward 1.32 -> 0.54 ms, dX 0.77
 // (GEMM + seq2col_bwd) -> 0.47 ms, stage 1 + dX 1.02 + 0.48 -> 0.80 ms
@@ -606,13 +607,17 @@ __global__ void mwe_bwd_stage1_kernel(
 // are returned in dg_out / db_out / dbias_out for mwe_colsums_park.  (They
 // accumulate in locals and are copied out at the end: accumulating through
 // the references keeps the arrays out of registers — 256 VGPRs and scratch.)
-template <int W, int NT, int AP, int HALO>
+// With COMPACT the tile's own rows of dM (the value scattered above, before
+// the piece expansion) also leave for memory as [T, W], straight from the
+// registers: the input of mwe_bwd_dw_kernel (srx_mwe_dw.hip.h).
+template <int W, int NT, int AP, int HALO, bool COMPACT = false>
 __device__ __forceinline__ void mwe_stage1_tile(
     const bf16_t* __restrict__ dY, const bf16_t* __restrict__ dropmask,
     const bf16_t* __restrict__ Mout, const bf16_t* __restrict__ g,
     const float* __restrict__ mu, const float* __restrict__ rstd,
     const uint8_t* __restrict__ which, long T, long t0, int tid, bf16_t* ldsA,
-    float (&dg_out)[8], float (&db_out)[8], float (&dbias_out)[3][8]) {
+    float (&dg_out)[8], float (&db_out)[8], float (&dbias_out)[3][8],
+    bf16_t* __restrict__ dMout = nullptr) {
   constexpr int MT = 128, A_ROWS = MT + 2 * HALO;
   constexpr int Q = W / 8;                        // 16-byte groups per row
   constexpr int RG = NT / 16;                     // rows per prologue pass
@@ -694,6 +699,12 @@ __device__ __forceinline__ void mwe_stage1_tile(
         for (int p = 0; p < 3; p++) dbias_loc[p][j] += (wh[j] == (uint32_t)p) ? dM : 0.f;
       }
     }
+    if (COMPACT && own) {
+      srx_u32x4_t o;
+#pragma unroll
+      for (int k = 0; k < 4; k++) o[k] = hb[2 * k] | (hb[2 * k + 1] << 16);
+      *(srx_u32x4_t*)(dMout + t * W + q * 8) = o;
+    }
     // expanded row: dM at piece `which`, exact zero in the other two
     if (qv && i < A_ROWS) {
 #pragma unroll
@@ -763,7 +774,7 @@ __device__ __forceinline__ void mwe_colsums_out(const float* ldsC,
   }
 }
 
-template <int W>
+template <int W, bool COMPACT = false>
 __global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
     const bf16_t* __restrict__ dY,        // [T, W]
     const bf16_t* __restrict__ dropmask,  // [T, W] or nullptr
@@ -775,7 +786,7 @@ __global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
     const bf16_t* __restrict__ WT,        // [3W, 3W] = weight^T, row-major
     const uint8_t* __restrict__ is_start,
     const uint8_t* __restrict__ is_end,
-    bf16_t* __restrict__ dPre,            // [T, 3W]
+    bf16_t* __restrict__ dPre,            // [T, 3W]; COMPACT: dM [T, W]
     bf16_t* __restrict__ dX,              // [T, W]
     float* __restrict__ partials,         // [gridDim.x, 5W]
     long T) {
@@ -802,8 +813,9 @@ __global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
   mwe_b_fetch<C>(WT, 0, tid, pf);
 
   float dg_loc[8], db_loc[8], dbias_loc[3][8];
-  mwe_stage1_tile<W, NT, AP, 1>(dY, dropmask, Mout, g, mu, rstd, which, T, t0,
-                                tid, ldsA, dg_loc, db_loc, dbias_loc);
+  mwe_stage1_tile<W, NT, AP, 1, COMPACT>(dY, dropmask, Mout, g, mu, rstd, which,
+                                         T, t0, tid, ldsA, dg_loc, db_loc,
+                                         dbias_loc, dPre);
 
   int zmask[2];
   mwe_section_masks<C>(is_start, is_end, T, t0, mh, lane, zmask);
@@ -811,7 +823,8 @@ __global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
   __syncthreads();
 
   // ---- dPre out: the tile's own rows, before the epilogue reuses the image
-  for (int id = tid; id < MT * (3 * Q); id += NT) {
+  // (COMPACT: dM has already left from the prologue's registers)
+  for (int id = tid; !COMPACT && id < MT * (3 * Q); id += NT) {
     const int r = id / (3 * Q), c = id % (3 * Q);
     if (t0 + r < T)
       *(srx_u32x4_t*)(dPre + (t0 + r) * (3 * W) + c * 8) =

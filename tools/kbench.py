@@ -578,7 +578,82 @@ def bench_mixer():
                   f"max {v[-1]:7.3f}{extra}")
 
 
+def bench_mwe_dw():
+    """MWE backward, dW path: old = full mwe_bwd_fused (writes dPre [T, 3W]) +
+    seq2col_fwd + mm_dw_chunked; new = compact mwe_bwd_fused (writes dM
+    [T, W]) + mwe_bwd_dw.  T = 1M, W = 96, with mask, docs of 20 tokens.  The
+    two paths alternate in one loop; median (min) of 30 event-timed calls
+    after 10 warm-ups, each piece timed on its own as well.  Bytes of
+    mwe_bwd_dw: dM + which + X + the boundary bytes (the 505 MB floor)."""
+    from spacy_ray_amd import _srx_hip as hip
+    from spacy_ray_amd.ops import api as ops
+
+    T, W = 1 << 20, 96
+    bf = torch.bfloat16
+    X = (torch.randn(T, W, device=dev) * 0.5).to(bf)
+    Wt = (torch.randn(3 * W, 3 * W, device=dev) / (3 * W) ** 0.5).to(bf)
+    bias = torch.zeros(3 * W, device=dev, dtype=bf)
+    g = torch.ones(W, device=dev, dtype=bf)
+    b = torch.zeros(W, device=dev, dtype=bf)
+    lens = torch.full((T // 20 + 1,), 20, device=dev, dtype=torch.long)
+    lens[-1] = T - 20 * (T // 20)
+    starts, ends = ops.boundary_masks_u8(lens, T)
+    mask = ops.dropout_mask_like(torch.empty(T, W, device=dev, dtype=bf), 0.1)
+    _, Mout, which, mu, rstd = hip.mwe_layer_fwd(X, Wt, bias, g, b, starts, ends,
+                                                 mask, 1e-5)
+    dY = torch.randn(T, W, device=dev).to(bf)
+
+    def fused_full():
+        return hip.mwe_bwd_fused(dY, mask, Mout, g, mu, rstd, which, Wt, starts,
+                                 ends)
+
+    def fused_compact():
+        return hip.mwe_bwd_fused(dY, mask, Mout, g, mu, rstd, which, Wt, starts,
+                                 ends, compact=True)
+
+    dPre = fused_full()[0]
+    dM = fused_compact()[0]
+    X3 = hip.seq2col_fwd(X, starts, ends)
+    pieces = {
+        "old: mwe_bwd_fused (dPre)": fused_full,
+        "old: seq2col_fwd": lambda: hip.seq2col_fwd(X, starts, ends),
+        "old: mm_dw_chunked": lambda: ops.mm_dw_chunked(dPre, X3),
+        "old: total": lambda: ops.mm_dw_chunked(
+            fused_full()[0], hip.seq2col_fwd(X, starts, ends)),
+        "new: mwe_bwd_fused (dM)": fused_compact,
+        "new: mwe_bwd_dw": lambda: hip.mwe_bwd_dw(dM, which, X, starts, ends),
+        "new: total": lambda: hip.mwe_bwd_dw(fused_compact()[0], which, X, starts,
+                                             ends),
+    }
+    ts = {k: [] for k in pieces}
+    for it in range(40):
+        for name, fn in pieces.items():
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= 10:
+                ts[name].append(e0.elapsed_time(e1))
+    dw_bytes = T * (2 * W * 2 + W + 2)
+    for name, v in ts.items():
+        v = sorted(v)
+        med = v[len(v) // 2]
+        extra = ""
+        if name == "new: mwe_bwd_dw":
+            extra = (f"  {dw_bytes / 1e6:.0f} MB -> {dw_bytes / med / 1e9:.2f} TB/s"
+                     " (incl. the partial reduction)")
+        print(f"  mwe_dw {name:28s} median {med:7.3f} ms  min {v[0]:7.3f} "
+              f"max {v[-1]:7.3f}{extra}")
+    a = pieces["old: total"]().float()
+    c = pieces["new: total"]().float()
+    print(f"  mwe_dw max |old - new| {float((a - c).abs().max()):.3e} at max |dW| "
+          f"{float(c.abs().max()):.3e}")
+
+
 ALL = {"mwe": bench_mwe, "dpre": bench_dpre, "ce": bench_ce, "mixer": bench_mixer,
+       "mwe_dw": bench_mwe_dw,
        "floret": bench_floret, "vecloss": bench_vecloss,
        "gpustate": bench_gpustate, "attn": bench_attn,
        "static_vectors": bench_static_vectors,
