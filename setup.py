@@ -10,6 +10,8 @@ Two extensions:
     systems).  Plain g++, no GPU needed.
   * spacy_ray_amd._srx_hip — CDNA4 (gfx950) HIP kernels as a torch extension;
     hipcc cross-compiles on a GPU-less box (PYTORCH_ROCM_ARCH=gfx950).
+  * spacy_ray_amd._srx_hip_vecsim — the cosine top-n kernels
+    (srx_vecsim_ext.hip), compiled with packed fp32 instructions off.
 """
 import os
 import sys
@@ -41,7 +43,10 @@ ext_modules = [
 
 cmdclass = {}
 # exclude hipify-generated *_hip.hip artifacts from previous builds
-hip_sources = [p for p in sorted(KERNELS.glob("*.hip")) if not p.name.endswith("_hip.hip")]
+# srx_vecsim_ext.hip is an extension of its own (other compiler flags)
+VECSIM_SRC = KERNELS / "srx_vecsim_ext.hip"
+hip_sources = [p for p in sorted(KERNELS.glob("*.hip"))
+               if not p.name.endswith("_hip.hip") and p != VECSIM_SRC]
 if hip_sources and "SRX_SKIP_HIP" not in os.environ:
     from torch.utils.cpp_extension import BuildExtension, CUDAExtension
 
@@ -55,6 +60,19 @@ if hip_sources and "SRX_SKIP_HIP" not in os.environ:
             },
         )
     )
+    if VECSIM_SRC.exists():
+        # no v_pk_{add,mul,fma}_f32 in this module: scalar fp32 VALU only
+        no_packed_fp32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+        ext_modules.append(
+            CUDAExtension(
+                "spacy_ray_amd._srx_hip_vecsim",
+                sources=[str(VECSIM_SRC)],
+                extra_compile_args={
+                    "cxx": ["-O3", "-std=c++17"],
+                    "nvcc": ["-O3", "-std=c++17"] + no_packed_fp32,
+                },
+            )
+        )
     cmdclass["build_ext"] = BuildExtension
 
 setup(

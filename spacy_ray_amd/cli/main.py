@@ -214,6 +214,7 @@ def init_vectors_cli(
     vectors_loc: Path = typer.Argument(..., help="word2vec text file, or a .floret table with --mode floret (.gz too)"),
     output_dir: Path = typer.Argument(..., help="Pipeline directory to write"),
     truncate: int = typer.Option(0, "--truncate", "-t", help="Keep only the first N vectors (0 = all)"),
+    prune: int = typer.Option(0, "--prune", "-p", help="Keep only the first N rows and point every other word at its most similar kept row (0 = off)"),
     name: str = typer.Option("", "--name", "-n", help="Name of the table (default: <lang>_vectors)"),
     mode: str = typer.Option("default", "--mode", "-m", help="'default': word2vec text, one row per word; 'floret': a .floret hashed n-gram table"),
 ):
@@ -224,7 +225,7 @@ def init_vectors_cli(
 
     try:
         nlp = init_vectors(lang, vectors_loc, output_dir, truncate=truncate,
-                           name=name or None, mode=mode)
+                           name=name or None, mode=mode, prune=prune)
     except ValueError as e:
         raise SystemExit(f"[x] {e}")
     print(f"[+] wrote {output_dir}: {nlp.vocab.vectors!r}")

@@ -605,6 +605,111 @@ def vectors_loss(pred: torch.Tensor, table: torch.Tensor, rows: torch.Tensor,
     return _VectorsLoss.apply(pred, table.detach(), rows, loss, float(scale))
 
 
+# ---------------------------------------------------- vectors most_similar
+# Cosine top-n over the vectors table (srx_vecsim.hip.h, in the extension
+# module _srx_hip_vecsim) against the composed path
+# (torch_ref.vectors_most_similar: normalise, mm in batches, sort).  Same
+# rule as vectors_loss: fused by default only where tools/kbench.py
+# most_similar measured it not slower on both of its shapes
+# (profiles/README.md); SRX_MOST_SIMILAR=fused / composed overrides.
+VECTORS_MOST_SIMILAR_FUSED_DEFAULT = True
+VECTORS_MOST_SIMILAR_MAX_N = 8
+
+_VECSIM = None
+_VECSIM_TRIED = False
+
+
+def hip_vecsim_ext():
+    global _VECSIM, _VECSIM_TRIED
+    if not _VECSIM_TRIED:
+        _VECSIM_TRIED = True
+        try:
+            from spacy_ray_amd import _srx_hip_vecsim  # noqa: F401
+            _VECSIM = _srx_hip_vecsim
+        except ImportError:
+            _VECSIM = None
+    return _VECSIM
+
+
+def vectors_most_similar_available(queries: torch.Tensor, table: torch.Tensor,
+                                   n: int = 1) -> bool:
+    """The kernel needs bf16 queries [nQ, nMp] and the bf16 padded table [V,
+    nMp] (nMp a multiple of 32, <= 320, both contiguous, pad columns zero),
+    1 <= n <= min(8, V) and the extension."""
+    if queries.dim() != 2 or table.dim() != 2:
+        return False
+    nMp = table.shape[1]
+    return (
+        queries.is_cuda
+        and table.is_cuda
+        and queries.dtype == torch.bfloat16
+        and table.dtype == torch.bfloat16
+        and queries.shape[1] == nMp
+        and nMp % 32 == 0
+        and 32 <= nMp <= 320
+        and 1 <= n <= min(VECTORS_MOST_SIMILAR_MAX_N, table.shape[0])
+        and queries.is_contiguous()
+        and table.is_contiguous()
+        and hip_vecsim_ext() is not None
+    )
+
+
+def _vectors_most_similar_fused(queries, table, n) -> bool:
+    mode = os.environ.get("SRX_MOST_SIMILAR", "")
+    if mode not in ("", "fused", "composed"):
+        raise ValueError(
+            f"SRX_MOST_SIMILAR={mode!r}: expected 'fused' or 'composed'")
+    if mode == "composed" or not queries.is_cuda:
+        return False
+    # a GPU run without the extension is an error, as elsewhere
+    _want_hip(queries)
+    if hip_vecsim_ext() is None and os.environ.get("SRX_ALLOW_TORCH_FALLBACK") != "1":
+        raise RuntimeError(
+            "spacy_ray_amd._srx_hip_vecsim (gfx950 cosine top-n kernels) is not "
+            "built but vectors_most_similar ran on a GPU tensor. Build with "
+            "`python setup.py build_ext --inplace`.")
+    if not vectors_most_similar_available(queries, table, n):
+        return False
+    return mode == "fused" or VECTORS_MOST_SIMILAR_FUSED_DEFAULT
+
+
+def vectors_row_inv(table: torch.Tensor) -> torch.Tensor:
+    """fp32 [V]: 1 / |row| of the bf16 device table, 0 for an all-zero row —
+    the pre-pass of the fused vectors_most_similar, for callers that query
+    one table many times."""
+    if hip_vecsim_ext() is None or not table.is_cuda:
+        raise RuntimeError("vectors_row_inv needs the _srx_hip_vecsim extension "
+                           "and a GPU table")
+    return hip_vecsim_ext().vectors_row_inv(table)
+
+
+def vectors_most_similar(queries: torch.Tensor, table: torch.Tensor, n: int = 1,
+                         *, splits: int = 0,
+                         table_inv: Optional[torch.Tensor] = None):
+    """Per query the n table rows of highest cosine similarity: (rows int32
+    [nQ, n], scores [nQ, n]), sorted by (score descending, row ascending);
+    scores are clipped to [-1, 1] and a zero vector scores 0 against
+    everything.  queries [nQ, W] and table [V, W] have the same width.
+
+    On a GPU, bf16 queries against the bf16 padded device table (both in the
+    Vectors.device_table layout, width <= 320) with n <= 8 run as the fused
+    MFMA kernel, which never writes the [nQ, V] similarity matrix; `splits`
+    (0 = automatic) is the number of workgroups that share one query tile's
+    table rows and `table_inv` an optional cached vectors_row_inv(table).
+    The result does not depend on either.  Everything else takes the
+    composed path.  SRX_MOST_SIMILAR=fused|composed overrides the default."""
+    if queries.dim() != 2 or table.dim() != 2 or queries.shape[1] != table.shape[1]:
+        raise ValueError("vectors_most_similar: queries [nQ, W] and table [V, W] "
+                         "must have the same width")
+    if not 1 <= n <= table.shape[0]:
+        raise ValueError(
+            f"vectors_most_similar: n = {n} outside 1..{table.shape[0]}")
+    if _vectors_most_similar_fused(queries, table, n):
+        return hip_vecsim_ext().vectors_most_similar(queries, table, int(n),
+                                                     int(splits), table_inv)
+    return ref.vectors_most_similar(queries, table, n)
+
+
 # ------------------------------------------------------------- layernorm
 class _LayerNorm(torch.autograd.Function):
     @staticmethod

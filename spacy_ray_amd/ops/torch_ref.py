@@ -179,6 +179,43 @@ def vectors_loss(pred: torch.Tensor, table: torch.Tensor, rows: torch.Tensor,
     return row_loss, dp.to(pred.dtype)
 
 
+def vectors_most_similar(queries: torch.Tensor, table: torch.Tensor, n: int = 1,
+                         batch_size: int = 1024):
+    """queries [nQ, W], table [V, W] -> (rows int32 [nQ, n], scores [nQ, n] in
+    the compute type): per query the n table rows of highest cosine
+    similarity, sorted by (score descending, row ascending).  Composed from
+    torch ops: both sides normalised (a zero norm becomes 1, so a zero vector
+    scores 0), `mm` over `batch_size` queries at a time, a stable descending
+    sort, the first n.  The compute type is the inputs' for fp64 and bf16 /
+    fp16 (as the library GEMM would run it) and fp32 otherwise; scores are
+    clipped to [-1, 1]."""
+    if queries.dim() != 2 or table.dim() != 2 or queries.shape[1] != table.shape[1]:
+        raise ValueError("vectors_most_similar: queries [nQ, W] and table [V, W] "
+                         "must have the same width")
+    V = table.shape[0]
+    if not 1 <= n <= V:
+        raise ValueError(f"vectors_most_similar: n = {n} outside 1..{V}")
+    ct = queries.dtype if queries.dtype.is_floating_point else torch.float32
+
+    def unit(x):
+        x = x.to(ct)
+        norm = x.float().norm(dim=1, keepdim=True) if ct != torch.float64 \
+            else x.norm(dim=1, keepdim=True)
+        return x / norm.masked_fill(norm == 0, 1).to(ct)
+
+    tn = unit(table).t()
+    rows, scores = [], []
+    for i in range(0, queries.shape[0], max(int(batch_size), 1)):
+        sims = unit(queries[i:i + batch_size]).mm(tn).clamp_(-1, 1)
+        s, r = sims.sort(dim=1, descending=True, stable=True)
+        rows.append(r[:, :n].to(torch.int32))
+        scores.append(s[:, :n])
+    if not rows:
+        return (torch.zeros(0, n, dtype=torch.int32, device=queries.device),
+                torch.zeros(0, n, dtype=ct, device=queries.device))
+    return torch.cat(rows), torch.cat(scores)
+
+
 def layernorm(X: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float = 1e-5):
     mu = X.mean(dim=-1, keepdim=True)
     var = X.var(dim=-1, unbiased=False, keepdim=True)

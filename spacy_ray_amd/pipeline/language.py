@@ -466,10 +466,12 @@ def load_init_vectors(nlp: Language, cfg: Dict) -> None:
 
 def init_vectors(lang: str, vectors_loc, output_dir, *, truncate: int = 0,
                  name: Optional[str] = None, mode: str = "default",
-                 key_attr: str = "ORTH") -> Language:
+                 key_attr: str = "ORTH", prune: int = 0) -> Language:
     """word2vec text file (mode "default") or floret's `.floret` table
     (mode "floret") -> a pipeline directory with an empty pipeline and a
-    vocab that holds the vectors (`spacy-mi init vectors`)."""
+    vocab that holds the vectors (`spacy-mi init vectors`).  prune = N > 0
+    keeps the first N rows (after `truncate`) and points every other word
+    at its most similar kept row (Vocab.prune_vectors)."""
     from spacy_ray_amd.vocab.vectors import (
         MODES, Vectors, read_floret_text, read_word2vec_text)
 
@@ -481,6 +483,10 @@ def init_vectors(lang: str, vectors_loc, output_dir, *, truncate: int = 0,
             raise ValueError(
                 "--truncate cannot be used with --mode floret: every row of "
                 "a hashed n-gram table is needed")
+        if prune:
+            raise ValueError(
+                "--prune cannot be used with --mode floret: a hashed n-gram "
+                "table has no word rows to merge")
         data, settings = read_floret_text(vectors_loc)
         nlp = build_nlp(config)
         nlp.vocab.vectors = Vectors(data, mode="floret", key_attr=key_attr,
@@ -493,6 +499,10 @@ def init_vectors(lang: str, vectors_loc, output_dir, *, truncate: int = 0,
                                            name=name or f"{lang}_vectors")
     for w in words:
         nlp.vocab.strings.add(w)
+    if prune < 0:
+        raise ValueError(f"init vectors --prune must be >= 0, got {prune}")
+    if prune:
+        nlp.vocab.prune_vectors(prune)
     nlp.to_disk(output_dir)
     return nlp
 

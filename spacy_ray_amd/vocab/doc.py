@@ -57,6 +57,36 @@ class Vocab:
             return np.zeros(self.vectors.width, dtype=np.float32)
         return self.vectors.data[row].copy()
 
+    def prune_vectors(self, nr_row: int, batch_size: int = 1024):
+        """Reduce the table to its first `nr_row` rows (spaCy's
+        Vocab.prune_vectors): every word of a dropped row is pointed at the
+        most similar kept row (Vectors.pruned) and `self.vectors` is
+        replaced.  Returns {word: (synonym, score)} for the remapped words
+        whose strings are in `self.strings`; the synonym is the first word
+        of the kept row.  nr_row >= len(vectors) changes nothing and
+        returns {}."""
+        if self.vectors is None:
+            raise ValueError("Vocab.prune_vectors: no vectors are loaded")
+        old = self.vectors
+        old._no_rows("prune_vectors")
+        if nr_row >= len(old):
+            return {}
+        new, new_rows, scores = old.pruned(nr_row, batch_size=batch_size)
+        row_keys = new._row_keys()
+        # the first word of a kept row is one that had it before pruning
+        kept = old.rows < nr_row
+        first_kept = np.zeros(nr_row, dtype=np.uint64)
+        rows, first = np.unique(old.rows[kept], return_index=True)
+        first_kept[rows] = old.keys[kept][first]
+        row_keys = np.where(first_kept != 0, first_kept, row_keys)
+        remap: Dict[str, tuple] = {}
+        for i in np.flatnonzero(~kept):
+            key, syn = int(old.keys[i]), int(row_keys[new_rows[i]])
+            if key in self.strings and syn in self.strings:
+                remap[self.strings[key]] = (self.strings[syn], float(scores[i]))
+        self.vectors = new
+        return remap
+
 
 class Doc:
     __slots__ = (

@@ -243,6 +243,99 @@ class Vectors:
             self._device[key] = table
         return table
 
+    # -------------------------------------------------- nearest neighbours
+    def _row_keys(self) -> np.ndarray:
+        """uint64 [V]: the first key, in sorted-key order, that maps to each
+        row; 0 for a row no key points at."""
+        out = np.zeros(len(self), dtype=np.uint64)
+        rows, first = np.unique(self.rows, return_index=True)
+        out[rows] = self.keys[first]
+        return out
+
+    def most_similar(self, queries: np.ndarray, *, batch_size: int = 1024,
+                     n: int = 1, sort: bool = True, device=None):
+        """For each query vector the n most similar table rows by cosine
+        similarity (spaCy's Vectors.most_similar): (keys uint64 [nQ, n], rows
+        int32 [nQ, n], scores float32 [nQ, n]), best first, equal scores by
+        ascending row.  keys[i, j] is the first key (in sorted-key order)
+        that maps to rows[i, j], 0 when none does.  A zero vector on either
+        side scores 0; scores are clipped to [-1, 1], not rounded.
+
+        device=None uses the GPU when there is one and the kernels are built,
+        else the CPU.  On the GPU the ranking is computed from the bf16 device
+        table with fp32 accumulation (ops.vectors_most_similar: the fused
+        kernel for n <= 8 and widths <= 320, otherwise composed in fp32); the
+        CPU path is fp32, composed, `batch_size` queries at a time.  The
+        result is always sorted, which `sort=False` permits."""
+        import torch
+
+        from spacy_ray_amd.ops import api as ops
+        from spacy_ray_amd.ops import torch_ref as ref
+
+        self._no_rows("most_similar")
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.width:
+            raise ValueError(
+                f"Vectors.most_similar: queries must be [nQ, {self.width}], "
+                f"got {queries.shape}")
+        V = len(self)
+        if not 1 <= n <= V:
+            raise ValueError(f"Vectors.most_similar: n = {n} outside 1..{V}")
+        if device is None:
+            gpu = torch.cuda.is_available() and ops.hip_vecsim_ext() is not None
+            device = "cuda" if gpu else "cpu"
+        device = torch.device(device)
+        q = torch.from_numpy(queries)
+        if device.type == "cpu":
+            rows, scores = ref.vectors_most_similar(
+                q, torch.from_numpy(self.data), n, batch_size)
+        elif n <= ops.VECTORS_MOST_SIMILAR_MAX_N and roundup(self.width, 32) <= 320:
+            table = self.device_table(device, torch.bfloat16)
+            qd = torch.zeros(len(q), table.shape[1], dtype=torch.bfloat16,
+                             device=device)
+            qd[:, :self.width] = q.to(device)
+            inv = None
+            if ops.hip_vecsim_ext() is not None:
+                key = (str(table.device), "row_inv")
+                inv = self._device.get(key)
+                if inv is None:
+                    inv = self._device[key] = ops.vectors_row_inv(table)
+            rows, scores = ops.vectors_most_similar(qd, table, n, table_inv=inv)
+        else:
+            rows, scores = ops.vectors_most_similar(
+                q.to(device), self.device_table(device, torch.float32), n)
+        rows = rows.cpu().numpy().astype(np.int32)
+        scores = scores.float().cpu().numpy()
+        return self._row_keys()[rows], rows, scores
+
+    def pruned(self, nr_row: int, *, batch_size: int = 1024, device=None):
+        """Keep rows 0 .. nr_row - 1 (file order, by convention frequency
+        order) and point every key of a dropped row at the most similar kept
+        row, one query per distinct dropped row.  Returns (Vectors with
+        nr_row rows and all keys, remap_rows int32 parallel to self.keys: the
+        new row of each key, scores float32 parallel to self.keys: 1.0 for a
+        key that kept its row, else the similarity to its new row)."""
+        self._no_rows("pruned")
+        nr_row = int(nr_row)
+        if nr_row < 1:
+            raise ValueError(f"Vectors.pruned: nr_row = {nr_row}: expected >= 1")
+        new_rows = self.rows.copy()
+        scores = np.ones(len(self.keys), dtype=np.float32)
+        if nr_row >= len(self):
+            return self, new_rows, scores
+        kept = Vectors(self.data[:nr_row], np.zeros(0, dtype=np.uint64),
+                       np.zeros(0, dtype=np.int32))
+        dropped = self.rows >= nr_row
+        distinct, inverse = np.unique(self.rows[dropped], return_inverse=True)
+        if len(distinct):
+            _, nbr, sc = kept.most_similar(self.data[distinct], n=1,
+                                           batch_size=batch_size, device=device)
+            new_rows[dropped] = nbr[:, 0][inverse]
+            scores[dropped] = sc[:, 0][inverse]
+        out = Vectors(self.data[:nr_row].copy(), self.keys, new_rows,
+                      name=self.name, key_attr=self.key_attr)
+        return out, new_rows, scores
+
     # ------------------------------------------------------- serialisation
     def to_disk(self, vocab_dir) -> None:
         from safetensors.numpy import save_file

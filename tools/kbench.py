@@ -516,6 +516,72 @@ def bench_vecloss():
               f"max |dPred fused - composed| = {diff:.3e}")
 
 
+def bench_most_similar():
+    """vectors_most_similar (srx_vecsim.hip.h) against the composed path
+    (torch_ref.vectors_most_similar in bf16, batch 1024) on the same inputs,
+    nM = 300 (row stride 320).  Pruning shape: nQ = 200k queries, V = 20k
+    rows, n = 1.  Interactive shape: nQ = 1, V = 1M, n = 8, with the
+    launcher's split count and with splits = 1.  The composed path is also
+    timed with torch.topk in place of the stable sort (no tie order, so not
+    the same contract, but the cheapest composed form).  The fused path is
+    timed with its inv(t) pre-pass and, as Vectors.most_similar calls it,
+    with the cached vectors_row_inv(table).  The paths alternate in one loop; median
+    of 30 event-timed calls after 10 warm-ups."""
+    from spacy_ray_amd.ops import api as ops
+    from spacy_ray_amd.ops import torch_ref as ref
+
+    vs = ops.hip_vecsim_ext()
+    assert vs is not None, "_srx_hip_vecsim is not built"
+    nM, nMp = 300, 320
+
+    def composed_topk(q, t, n):
+        unit = lambda x: x / x.float().norm(dim=1, keepdim=True).clamp_(min=1e-30).to(x.dtype)
+        tn = unit(t).t()
+        out = [unit(q[i:i + 1024]).mm(tn).topk(n, dim=1) for i in range(0, len(q), 1024)]
+        return torch.cat([o.indices for o in out]), torch.cat([o.values for o in out])
+
+    for label, nQ, V, n, split_list in (("pruning", 200_000, 20_000, 1, (0,)),
+                                        ("interactive", 1, 1_000_000, 8, (0, 1))):
+        table = torch.zeros(V, nMp, device=dev, dtype=torch.bfloat16)
+        table[:, :nM] = torch.randn(V, nM, device=dev) * 0.5
+        q = torch.zeros(nQ, nMp, device=dev, dtype=torch.bfloat16)
+        q[:, :nM] = torch.randn(nQ, nM, device=dev) * 0.5
+        inv = vs.vectors_row_inv(table)
+        fns = {f"fused splits={s}": (lambda s=s: vs.vectors_most_similar(q, table, n, s))
+               for s in split_list}
+        fns["fused, cached inv"] = lambda: vs.vectors_most_similar(q, table, n, 0, inv)
+        fns["composed sort"] = lambda: ref.vectors_most_similar(q, table, n, 1024)
+        fns["composed topk"] = lambda: composed_topk(q, table, n)
+        rows_f = fns[f"fused splits={split_list[0]}"]()[0]
+        rows_c = fns["composed sort"]()[0]
+        agree = (rows_f[:, 0] == rows_c[:, 0]).float().mean().item()
+        for _ in range(10):
+            for fn in fns.values():
+                fn()
+        torch.cuda.synchronize()
+        times = {k: [] for k in fns}
+        for _ in range(30):
+            for name, fn in fns.items():
+                a = torch.cuda.Event(enable_timing=True)
+                b = torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                times[name].append(a.elapsed_time(b))
+        flops = 2.0 * nQ * V * nMp
+        print(f"most_similar {label} (nQ={nQ}, V={V}, nM={nM}, n={n}): top-1 rows "
+              f"fused == composed on {agree:.4f} of the queries; similarity matrix "
+              f"of the composed path: {nQ * V * 2 * 2 / 1e9:.3f} GB written + read "
+              f"in bf16 ({nQ * V * 4 * 2 / 1e9:.3f} GB in fp32)")
+        for name, ts in times.items():
+            ts.sort()
+            med = ts[len(ts) // 2]
+            print(f"  {name:18s} median {med:9.3f} ms  min {ts[0]:9.3f} ms  "
+                  f"{flops / med / 1e9:8.1f} TFLOP/s  "
+                  f"{V * nMp * 2 / med / 1e9:6.3f} TB/s of one table pass")
+
+
 def bench_mixer():
     """Fused mixer (mixer_fwd / mixer_bwd_fused + dW) against the composed
     chain (linear_cdw -> maxout -> layernorm -> * mask and its autograd
@@ -655,6 +721,7 @@ def bench_mwe_dw():
 ALL = {"mwe": bench_mwe, "dpre": bench_dpre, "ce": bench_ce, "mixer": bench_mixer,
        "mwe_dw": bench_mwe_dw,
        "floret": bench_floret, "vecloss": bench_vecloss,
+       "most_similar": bench_most_similar,
        "gpustate": bench_gpustate, "attn": bench_attn,
        "static_vectors": bench_static_vectors,
        "hashembed": bench_hashembed}
