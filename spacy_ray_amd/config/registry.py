@@ -50,6 +50,7 @@ class registry:
     appear in training configs)."""
 
     architectures = Registry("architectures")
+    layers = Registry("layers")
     optimizers = Registry("optimizers")
     schedules = Registry("schedules")
     batchers = Registry("batchers")

@@ -213,8 +213,37 @@ def make_textcat_reduce_model(tok2vec: ModelSpec,
     return spec
 
 
+@registry.layers("spacy.mean_max_reducer.v1")
+def make_mean_max_reducer(hidden_size: int = 128):
+    """spaCy's span reducer: last | first | mean | max over the span's
+    tokens, then Maxout(nO=hidden_size, nP=3, normalize=True).  Returns the
+    settings; SpancatPipe builds the head once the labels are known."""
+    if int(hidden_size) < 1:
+        raise ValueError("spacy.mean_max_reducer.v1: hidden_size must be >= 1")
+    return {"reducer": "mean_max", "hidden_size": int(hidden_size)}
+
+
+@registry.layers("spacy.LinearLogistic.v1")
+def make_linear_logistic(nO: Optional[int] = None, nI: Optional[int] = None):
+    """spaCy's span scorer: a linear layer whose logits go through a
+    sigmoid (in the loss and at prediction time)."""
+    return {"scorer": "linear_logistic"}
+
+
 @registry.architectures("spacy.SpanCategorizer.v1")
-def make_spancat_model(tok2vec: ModelSpec, **_ignored):
+def make_spancat_model(tok2vec: ModelSpec, reducer: Optional[dict] = None,
+                       scorer: Optional[dict] = None, **_ignored):
+    """Without a `reducer` block: mean pooling and one linear layer
+    (SpancatHead).  With `spacy.mean_max_reducer.v1`: spaCy's model, the
+    span-pool kernels + Maxout + linear-logistic scorer."""
+    for block, key in ((reducer, "reducer"), (scorer, "scorer")):
+        if block is not None and not (isinstance(block, dict) and key in block):
+            raise ValueError(
+                f"spacy.SpanCategorizer.v1: unsupported {key} block {block!r}")
+    if scorer is not None and reducer is None:
+        raise ValueError(
+            "spacy.SpanCategorizer.v1: a scorer block needs a reducer block")
     spec = ModelSpec(lambda: None, width=tok2vec.width, kind="spancat")
     spec.embedded_tok2vec = tok2vec if tok2vec.kind == "tok2vec" else None
+    spec.hidden_size = reducer["hidden_size"] if reducer else None
     return spec

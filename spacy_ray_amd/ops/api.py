@@ -605,6 +605,141 @@ def vectors_loss(pred: torch.Tensor, table: torch.Tensor, rows: torch.Tensor,
     return _VectorsLoss.apply(pred, table.detach(), rows, loss, float(scale))
 
 
+# ------------------------------------------------------------ span pooling
+# span_pool kernels (srx_spanpool.hip.h) against the composed path
+# (torch_ref.span_pool under autograd: a padded [S, max_len, W] gather and
+# elementwise passes).  Same rule as vectors_loss: fused by default only
+# where tools/kbench.py span_pool measured it not slower, forward and
+# backward both (docs/KERNELS.md, "Span pooling"); SRX_SPAN_POOL=fused /
+# composed overrides.
+# Measured (T = 1M tokens in 20-word docs, W = 96, bf16, 2.99M spans of 1..3
+# tokens): forward 0.829 ms against 30.256 ms, backward 0.906 ms against
+# 42.259 ms.
+SPAN_POOL_FUSED_DEFAULT = True
+SPAN_POOL_MAX_LEN = 255  # `which` is a byte
+
+
+class SpanIndex:
+    """A batch's candidate spans, ready for span_pool: int32 device tensors
+    `starts` / `ends` [S] and the token -> span CSR of the backward
+    (`tok_offsets` [T + 1], `tok_spans` [nnz], ascending span id per token),
+    plus n_spans, n_tokens and max_len as host ints.  Built on the host
+    (ops.span_index); cache it with the batch."""
+
+    __slots__ = ("starts", "ends", "tok_offsets", "tok_spans", "n_spans",
+                 "n_tokens", "max_len")
+
+
+def span_index(starts, ends, n_tokens: int, device) -> SpanIndex:
+    """Validate spans (0 <= start <= end <= n_tokens, else ValueError) and
+    build their SpanIndex from host integer arrays, without a device sync."""
+    import numpy as np
+
+    s = np.ascontiguousarray(np.asarray(starts, dtype=np.int64).reshape(-1))
+    e = np.ascontiguousarray(np.asarray(ends, dtype=np.int64).reshape(-1))
+    T = int(n_tokens)
+    if s.shape != e.shape:
+        raise ValueError("span_index: starts and ends differ in length")
+    if T < 0 or T >= 2 ** 31 or s.size >= 2 ** 31:
+        raise ValueError("span_index: sizes must fit in int32")
+    if s.size and (s.min() < 0 or (s > e).any() or e.max() > T):
+        raise ValueError(
+            f"span_index: need 0 <= start <= end <= n_tokens ({T}) for every span")
+    L = e - s
+    nnz = int(L.sum())
+    if nnz >= 2 ** 31:
+        raise ValueError("span_index: more than 2^31 (token, span) pairs")
+    # (token, span) pairs span-major, then a stable sort by token: the spans
+    # of one token stay in ascending id
+    span_of = np.repeat(np.arange(s.size, dtype=np.int64), L)
+    tok_of = np.arange(nnz, dtype=np.int64) - np.repeat(np.cumsum(L) - L - s, L)
+    order = np.argsort(tok_of, kind="stable")
+    offsets = np.zeros(T + 1, dtype=np.int64)
+    np.cumsum(np.bincount(tok_of, minlength=T), out=offsets[1:])
+
+    def dev(a):
+        return torch.from_numpy(a.astype(np.int32)).to(device)
+
+    idx = SpanIndex()
+    idx.starts, idx.ends = dev(s), dev(e)
+    idx.tok_offsets, idx.tok_spans = dev(offsets), dev(span_of[order])
+    idx.n_spans, idx.n_tokens = int(s.size), T
+    idx.max_len = int(L.max()) if s.size else 0
+    return idx
+
+
+def span_pool_available(X: torch.Tensor, index: SpanIndex) -> bool:
+    """The kernels take a contiguous bf16 (W % 8 == 0) or fp32 (W % 4 == 0)
+    X [T, W] on the GPU with W <= 1024, and spans of at most 255 tokens."""
+    if X.dim() != 2 or not X.is_cuda:
+        return False
+    per = {torch.bfloat16: 8, torch.float32: 4}.get(X.dtype)
+    W = X.shape[1]
+    return (
+        per is not None
+        and 0 < W <= 1024
+        and W % per == 0
+        and index.max_len <= SPAN_POOL_MAX_LEN
+        and hip_ext() is not None
+    )
+
+
+def _span_pool_fused(X: torch.Tensor, index: SpanIndex) -> bool:
+    mode = os.environ.get("SRX_SPAN_POOL", "")
+    if mode not in ("", "fused", "composed"):
+        raise ValueError(
+            f"SRX_SPAN_POOL={mode!r}: expected 'fused' or 'composed'")
+    if mode == "composed" or not X.is_cuda:
+        return False
+    _want_hip(X)  # a GPU run without the extension is an error, as elsewhere
+    if not span_pool_available(X, index):
+        return False
+    return mode == "fused" or SPAN_POOL_FUSED_DEFAULT
+
+
+class _SpanPool(torch.autograd.Function):
+    """Forward: one launch writes R (pad rows included) and `which`.
+    Backward: one gather launch over the token rows, no atomics."""
+
+    @staticmethod
+    def forward(ctx, X, index, rows):
+        R, which = hip_ext().span_pool_fwd(X.contiguous(), index.starts,
+                                           index.ends, rows)
+        ctx.save_for_backward(which)
+        ctx.index = index
+        return R
+
+    @staticmethod
+    def backward(ctx, dR):
+        (which,) = ctx.saved_tensors
+        ix = ctx.index
+        dX = hip_ext().span_pool_bwd(dR.contiguous(), which, ix.starts, ix.ends,
+                                     ix.tok_offsets, ix.tok_spans)
+        return dX, None, None
+
+
+def span_pool(X: torch.Tensor, index: SpanIndex, pad_rows: int = 1) -> torch.Tensor:
+    """spaCy's mean_max_reducer input: X [T, W] and the spans of `index` ->
+    R [roundup(S, pad_rows), 4 W] in X's dtype, R[s] = X[e-1] | X[a] | mean
+    | max over the span's tokens (an empty span gives a zero row), with
+    autograd to X; the whole max gradient goes to the first maximal token.
+    Pad rows are zero and pass no gradient.  On a GPU, bf16 / fp32 input
+    with spans of at most 255 tokens runs as one HIP launch each way
+    (span_pool_available); everything else takes torch_ref.span_pool.
+    SRX_SPAN_POOL=fused|composed overrides the default."""
+    if X.dim() != 2 or X.shape[0] != index.n_tokens:
+        raise ValueError("span_pool: X must be [index.n_tokens, W]")
+    S = index.n_spans
+    pad_rows = max(1, int(pad_rows))
+    rows = (S + pad_rows - 1) // pad_rows * pad_rows
+    if _span_pool_fused(X, index):
+        return _SpanPool.apply(X, index, rows)
+    R, _ = ref.span_pool(X, index.starts, index.ends, max_len=index.max_len)
+    if rows > S:
+        R = torch.cat([R, R.new_zeros(rows - S, R.shape[1])])
+    return R
+
+
 # ---------------------------------------------------- vectors most_similar
 # Cosine top-n over the vectors table (srx_vecsim.hip.h, in the extension
 # module _srx_hip_vecsim) against the composed path

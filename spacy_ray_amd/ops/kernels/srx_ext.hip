@@ -20,6 +20,7 @@
 #include "srx_staticvec.hip.h"
 #include "srx_floret.hip.h"
 #include "srx_vecloss.hip.h"
+#include "srx_spanpool.hip.h"
 #include "srx_activations.hip.h"
 #include "srx_attn.hip.h"
 
@@ -1892,6 +1893,128 @@ void vectors_loss(at::Tensor pred, at::Tensor table, at::Tensor rows,
 #undef SRX_VECLOSS_LAUNCH
 }
 
+// ------------------------------------------------------------ span pooling
+// see srx_spanpool.hip.h.  X [T, W] bf16 (W % 8 == 0) or fp32 (W % 4 == 0),
+// W <= 1024; starts / ends int32 [S].
+namespace spanpool {
+
+inline int sub_wave(long Q) { return Q <= 8 ? 8 : Q <= 16 ? 16 : Q <= 32 ? 32 : 64; }
+
+// memory bound: at most 8 workgroups per CU, the rest is grid-strided
+inline dim3 grid_for(long rows, int sw) {
+  const long per_block = (SRX_SPANPOOL_THREADS / SRX_WAVE) * (SRX_WAVE / sw);
+  const long cap = 8L * at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  return dim3((unsigned)std::max<long>(
+      1, std::min<long>((rows + per_block - 1) / per_block, cap)));
+}
+
+inline long check_x(const at::Tensor& X, const char* what) {
+  check_dev(X);
+  TORCH_CHECK(X.dim() == 2 && (X.scalar_type() == at::kBFloat16 ||
+                               X.scalar_type() == at::kFloat),
+              what, " must be bf16 or fp32 [rows, W]");
+  const long V = X.scalar_type() == at::kBFloat16 ? 8 : 4;
+  return V;
+}
+
+inline void check_spans(const at::Tensor& starts, const at::Tensor& ends) {
+  check_dev(starts);
+  check_dev(ends);
+  TORCH_CHECK(starts.scalar_type() == at::kInt && ends.scalar_type() == at::kInt &&
+                  starts.dim() == 1 && ends.dim() == 1 &&
+                  starts.numel() == ends.numel(),
+              "span_pool: starts and ends must be int32 [S]");
+}
+
+}  // namespace spanpool
+
+#define SRX_SPANPOOL_DISPATCH(LAUNCH)                                          \
+  if (bf16) {                                                                  \
+    if (sw == 8) { LAUNCH(bf16_t, 8); }                                        \
+    else if (sw == 16) { LAUNCH(bf16_t, 16); }                                 \
+    else if (sw == 32) { LAUNCH(bf16_t, 32); }                                 \
+    else { LAUNCH(bf16_t, 64); }                                               \
+  } else {                                                                     \
+    if (sw == 8) { LAUNCH(float, 8); }                                         \
+    else if (sw == 16) { LAUNCH(float, 16); }                                  \
+    else if (sw == 32) { LAUNCH(float, 32); }                                  \
+    else { LAUNCH(float, 64); }                                                \
+  }
+
+// -> (R [rows, 4 W], which uint8 [S, W]); rows >= S, rows [S, rows) zero
+std::vector<at::Tensor> span_pool_fwd(at::Tensor X, at::Tensor starts,
+                                      at::Tensor ends, long rows) {
+  const long V = spanpool::check_x(X, "span_pool_fwd: X");
+  spanpool::check_spans(starts, ends);
+  const long T = X.size(0), W = X.size(1), S = starts.numel();
+  TORCH_CHECK(W >= V && W % V == 0 && W <= 1024,
+              "span_pool_fwd: W must be a multiple of ", V, " and <= 1024");
+  TORCH_CHECK(rows >= S && rows < (1L << 31) && T < (1L << 31),
+              "span_pool_fwd: S <= rows < 2^31 and T < 2^31");
+  TORCH_CHECK(aligned16(X.data_ptr()), "span_pool_fwd: X not 16-byte aligned");
+  auto R = at::empty({rows, 4 * W}, X.options());
+  auto which = at::empty({S, W}, X.options().dtype(at::kByte));
+  if (rows == 0) return {R, which};
+  const bool bf16 = X.scalar_type() == at::kBFloat16;
+  const int sw = spanpool::sub_wave(W / V);
+  const dim3 grid = spanpool::grid_for(rows, sw);
+  auto stream = at::cuda::getCurrentCUDAStream();
+#define SRX_SPANPOOL_FWD(TT, SW)                                               \
+  hipLaunchKernelGGL((span_pool_fwd_kernel<TT, SW>), grid,                     \
+                     dim3(SRX_SPANPOOL_THREADS), 0, stream,                    \
+                     (const TT*)X.data_ptr(), starts.data_ptr<int>(),          \
+                     ends.data_ptr<int>(), (TT*)R.data_ptr(),                  \
+                     which.data_ptr<uint8_t>(), (int)S, (int)rows, (int)T,     \
+                     (int)W)
+  SRX_SPANPOOL_DISPATCH(SRX_SPANPOOL_FWD)
+#undef SRX_SPANPOOL_FWD
+  return {R, which};
+}
+
+// dX [T, W] from dR [>= S, 4 W]; every row of dX is written
+at::Tensor span_pool_bwd(at::Tensor dR, at::Tensor which, at::Tensor starts,
+                         at::Tensor ends, at::Tensor tok_offsets,
+                         at::Tensor tok_spans) {
+  const long V = spanpool::check_x(dR, "span_pool_bwd: dR");
+  spanpool::check_spans(starts, ends);
+  check_dev(which);
+  check_dev(tok_offsets);
+  check_dev(tok_spans);
+  const long S = starts.numel(), W = dR.size(1) / 4;
+  TORCH_CHECK(dR.size(1) == 4 * W && W >= V && W % V == 0 && W <= 1024 &&
+                  dR.size(0) >= S,
+              "span_pool_bwd: dR must be [>= S, 4 W], W a multiple of ", V,
+              " and <= 1024");
+  TORCH_CHECK(which.scalar_type() == at::kByte && which.dim() == 2 &&
+                  which.size(0) == S && which.size(1) == W,
+              "span_pool_bwd: which must be uint8 [S, W]");
+  TORCH_CHECK(tok_offsets.scalar_type() == at::kInt && tok_offsets.dim() == 1 &&
+                  tok_offsets.numel() >= 1 &&
+                  tok_spans.scalar_type() == at::kInt && tok_spans.dim() == 1,
+              "span_pool_bwd: tok_offsets int32 [T + 1], tok_spans int32 [nnz]");
+  const long T = tok_offsets.numel() - 1, nnz = tok_spans.numel();
+  TORCH_CHECK(T < (1L << 31) && nnz < (1L << 31) && S < (1L << 31),
+              "span_pool_bwd: sizes must fit in int32");
+  TORCH_CHECK(aligned16(dR.data_ptr()), "span_pool_bwd: dR not 16-byte aligned");
+  auto dX = at::empty({T, W}, dR.options());
+  if (T == 0) return dX;
+  const bool bf16 = dR.scalar_type() == at::kBFloat16;
+  const int sw = spanpool::sub_wave(W / V);
+  const dim3 grid = spanpool::grid_for(T, sw);
+  auto stream = at::cuda::getCurrentCUDAStream();
+#define SRX_SPANPOOL_BWD(TT, SW)                                               \
+  hipLaunchKernelGGL((span_pool_bwd_kernel<TT, SW>), grid,                     \
+                     dim3(SRX_SPANPOOL_THREADS), 0, stream,                    \
+                     (const TT*)dR.data_ptr(), which.data_ptr<uint8_t>(),      \
+                     starts.data_ptr<int>(), ends.data_ptr<int>(),             \
+                     tok_offsets.data_ptr<int>(), tok_spans.data_ptr<int>(),   \
+                     (TT*)dX.data_ptr(), (int)S, (int)T, (int)W, (int)nnz)
+  SRX_SPANPOOL_DISPATCH(SRX_SPANPOOL_BWD)
+#undef SRX_SPANPOOL_BWD
+  return dX;
+}
+#undef SRX_SPANPOOL_DISPATCH
+
 // --------------------------------------------- fused transition step (C++)
 // One python call per transition step: state scorer kernel + upper GEMM +
 // on-device action selection, with a C++ autograd node so the per-step
@@ -2058,7 +2181,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("vectors_loss", &vectors_loss, py::arg("pred"), py::arg("table"),
         py::arg("rows"), py::arg("row_loss"), py::arg("dpred"), py::arg("l2"),
         py::arg("scale"));
-  m.def("fused_step", &fusedstep::fused_step);
+  m.def("span_pool_fwd", &span_pool_fwd, py::arg("X"), py::arg("starts"),
+        py::arg("ends"), py::arg("rows"));
+  m.def("span_pool_bwd", &span_pool_bwd, py::arg("dR"), py::arg("which"),
+        py::arg("starts"), py::arg("ends"), py::arg("tok_offsets"),
+        py::arg("tok_spans"));
+  m.def("fused_step",&fusedstep::fused_step);
   m.def("fused_entries_take", &fusedstep::fused_entries_take);
   m.def("transition_ce", &transition_ce, py::arg("scores"), py::arg("gold"),
         py::arg("valid"), py::arg("deterministic") = false);

@@ -134,6 +134,51 @@ def floret_words_mean(table: torch.Tensor, offsets: torch.Tensor,
     return mean.to(table.dtype)
 
 
+def span_pool(X: torch.Tensor, starts: torch.Tensor, ends: torch.Tensor,
+              max_len: Optional[int] = None):
+    """X [T, W], spans [starts[s], ends[s]) -> (R [S, 4 W] in X's dtype,
+    which uint8 [S, W]): spaCy's mean_max_reducer input, R[s] = X[e-1] |
+    X[a] | mean | max over the span's tokens, which[s, c] the offset t - a
+    of the first token attaining the maximum (clamped to 255; meaningful for
+    spans of at most 256 tokens).  An empty span gives a zero row.  The mean
+    is an fp32 (fp64 for fp64 input) sum divided by the length.
+    Differentiable in X: the whole max gradient goes to that first token.
+    Bounds are clamped to [0, T] as in the kernel (srx_spanpool.hip.h).  A
+    padded [chunk, max_len, W] gather, so spans are taken in chunks; pass
+    max_len (the longest span) to spare the device sync that finds it."""
+    T, W = X.shape
+    a = starts.long().clamp(0, T)
+    e = torch.maximum(ends.long().clamp(0, T), a)
+    L = e - a
+    S = a.numel()
+    acc = torch.float64 if X.dtype == torch.float64 else torch.float32
+    if S == 0 or T == 0:
+        return (X.new_zeros(S, 4 * W) + 0 * X.sum(),
+                torch.zeros(S, W, dtype=torch.uint8, device=X.device))
+    Lm = max(1, int(L.max()) if max_len is None else int(max_len))
+    step = max(1, (1 << 24) // (Lm * W))
+    pos = torch.arange(Lm, device=X.device)
+    Xa = X.to(acc)  # gather and accumulate (the backward too) in fp32
+    Rs, whichs = [], []
+    for c in range(0, S, step):
+        ac, Lc = a[c:c + step], L[c:c + step]
+        live = (Lc > 0)[:, None]
+        valid = pos[None, :] < Lc[:, None]                      # [s, Lm]
+        G = Xa[(ac[:, None] + pos[None, :]).clamp(max=T - 1)]   # [s, Lm, W]
+        first = G[:, 0]
+        last = G[torch.arange(len(ac), device=X.device), (Lc - 1).clamp(min=0)]
+        mean = (G * valid[:, :, None]).sum(1) / Lc.clamp(min=1)[:, None].to(acc)
+        Gm = G.detach().masked_fill(~valid[:, :, None], float("-inf"))
+        at_max = Gm == Gm.amax(dim=1, keepdim=True)
+        which = torch.where(at_max, pos[None, :, None], Lm).amin(dim=1)
+        which = which.clamp(max=Lm - 1)                          # empty span
+        mx = G.gather(1, which[:, None, :]).squeeze(1)
+        Rc = torch.cat([last, first, mean, mx], dim=1).to(X.dtype)
+        Rs.append(torch.where(live, Rc, torch.zeros_like(Rc)))
+        whichs.append(torch.where(live, which, 0).clamp(max=255).to(torch.uint8))
+    return torch.cat(Rs), torch.cat(whichs)
+
+
 def vectors_loss(pred: torch.Tensor, table: torch.Tensor, rows: torch.Tensor,
                  loss: str = "cosine", scale: float = 1.0):
     """pred [N, nM], table [V, >= nM], rows [N] int -> (row_loss [N] in the

@@ -1343,6 +1343,34 @@ class SpancatHead(nn.Module):
         return linear_cdw(X, self.output.weight, self.output.bias)
 
 
+class SpancatReducerHead(nn.Module):
+    """spaCy's SpanCategorizer.v1 head: mean_max_reducer (last | first |
+    mean | max over the span's tokens, then Maxout(hidden, 3 pieces) +
+    LayerNorm) and a linear scorer whose logits go through a sigmoid.  The
+    pooling is ops.span_pool; the Maxout + LayerNorm runs as the fused mixer
+    kernels where they apply (bf16 on the GPU, hidden == width in {96, 128})
+    and as the composed Maxout module otherwise."""
+
+    def __init__(self, width: int, hidden_size: int, n_labels: int):
+        super().__init__()
+        from spacy_ray_amd.models.layers import Linear, Maxout
+
+        self.reduce = Maxout(4 * width, hidden_size, 3, normalize=True)
+        self.output = Linear(hidden_size, n_labels)
+
+    def forward(self, X, index):
+        from spacy_ray_amd.ops import api as ops
+
+        R = ops.span_pool(X, index, pad_rows=64)
+        m = self.reduce
+        if ops.mixer_layer_available(R, m.nO, m.pieces):
+            H = ops.mixer_layer(R, m.weight, m.bias, m.norm.weight,
+                                m.norm.bias, None, m.norm.eps)
+        else:
+            H = m(R)
+        return self.output(H[:index.n_spans])
+
+
 class SpancatPipe(TrainablePipe):
     """Span categorizer (spaCy's `spancat`): an ngram suggester (sizes
     1..max_ngram) over each doc plus a multi-label classifier on pooled
@@ -1351,7 +1379,8 @@ class SpancatPipe(TrainablePipe):
     sum of the tok2vec matrix — every candidate is two gathers and a
     divide, no per-span loops.  Gold/predictions live in
     `Doc.spans[spans_key]` as (start, end, label) triples; scored as
-    spans_sc_p/r/f."""
+    spans_sc_p/r/f.  A model with a `reducer` block (hidden_size set) uses
+    spaCy's mean-max reducer head instead (SpancatReducerHead)."""
 
     name = "spancat"
     listens_to = "tok2vec"
@@ -1365,6 +1394,7 @@ class SpancatPipe(TrainablePipe):
         self.name = name
         self.width = spec.width
         self.embedded_spec = getattr(spec, "embedded_tok2vec", None)
+        self.hidden_size = getattr(spec, "hidden_size", None)
         self.spans_key = spans_key
         self.max_ngram = int(max_ngram)
         self.threshold = float(threshold)
@@ -1381,9 +1411,17 @@ class SpancatPipe(TrainablePipe):
             self.label2id = {t: i for i, t in enumerate(self.labels)}
         self.cfg.update(labels=self.labels, spans_key=self.spans_key,
                         max_ngram=self.max_ngram, threshold=self.threshold)
+        if self.hidden_size:
+            self.cfg.update(hidden_size=int(self.hidden_size))
         if self.module is None:
-            self.module = SpancatHead(self.width, max(1, len(self.labels))).to(device)
+            self.module = self._make_head().to(device)
         self._attach_embedded(device)
+
+    def _make_head(self) -> nn.Module:
+        n_labels = max(1, len(self.labels))
+        if self.hidden_size:
+            return SpancatReducerHead(self.width, int(self.hidden_size), n_labels)
+        return SpancatHead(self.width, n_labels)
 
     def load_cfg(self, cfg, device) -> None:
         super().load_cfg(cfg, device)
@@ -1392,8 +1430,9 @@ class SpancatPipe(TrainablePipe):
         self.spans_key = cfg.get("spans_key", "sc")
         self.max_ngram = int(cfg.get("max_ngram", 3))
         self.threshold = float(cfg.get("threshold", 0.5))
+        self.hidden_size = cfg.get("hidden_size")
         if self.module is None:
-            self.module = SpancatHead(self.width, max(1, len(self.labels))).to(device)
+            self.module = self._make_head().to(device)
         self._attach_embedded(device)
 
     # ---------------------------------------------------------- candidates
@@ -1420,10 +1459,25 @@ class SpancatPipe(TrainablePipe):
         self._sugg_cache = (key, out)
         return out
 
+    def _span_index(self, lengths: np.ndarray, ss, ee, total: int, device):
+        """The batch's SpanIndex, cached like (and keyed as) _sugg_cache."""
+        from spacy_ray_amd.ops.api import span_index
+
+        key = (lengths.tobytes(), str(device))
+        cached = getattr(self, "_index_cache", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        index = span_index(ss, ee, total, device)
+        self._index_cache = (key, index)
+        return index
+
     def _span_scores(self, t2v, lengths: np.ndarray):
         device = t2v.device
         di, ss, ee = self._suggest(lengths)
         total = int(lengths.sum())
+        if self.hidden_size:
+            index = self._span_index(lengths, ss, ee, total, device)
+            return self.module(t2v[:total], index), di, ss, ee
         csum = torch.cumsum(t2v[:total].float(), dim=0)
         P = torch.cat([csum.new_zeros(1, csum.shape[1]), csum], dim=0)
         s_t = torch.from_numpy(ss).to(device)

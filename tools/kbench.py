@@ -718,10 +718,117 @@ def bench_mwe_dw():
           f"{float(c.abs().max()):.3e}")
 
 
+def _alternate(fns, iters=30, warmup=10):
+    """Median (and min) per-call GPU time of each fn, the fns alternating in
+    one loop so that clock and cache state are shared."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in fns}
+    for _ in range(iters):
+        for name, fn in fns.items():
+            a = torch.cuda.Event(enable_timing=True)
+            b = torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[name].append(a.elapsed_time(b))
+    out = {}
+    for name, ts in times.items():
+        ts.sort()
+        out[name] = (ts[len(ts) // 2], ts[0])
+    return out
+
+
+def bench_span_pool():
+    """span_pool (srx_spanpool.hip.h) against the composed path
+    (torch_ref.span_pool and its autograd backward) on the same inputs: T =
+    1,048,576 tokens in 20-word docs, W = 96, bf16, every 1..3-gram a span.
+    Forward and backward are timed separately; then the spancat reducer
+    head's scores + BCE loss, forward + backward, with both routes."""
+    import numpy as np
+
+    from spacy_ray_amd.ops import api as ops
+    from spacy_ray_amd.ops import torch_ref as ref
+    from spacy_ray_amd.pipeline.pipes import SpancatReducerHead
+
+    T, W, doc = 1 << 20, 96, 20
+    starts, ends = [], []
+    for off in range(0, T, doc):
+        n = min(doc, T - off)
+        for k in (1, 2, 3):
+            a = np.arange(off, off + max(0, n - k + 1))
+            starts.append(a)
+            ends.append(a + k)
+    starts, ends = np.concatenate(starts), np.concatenate(ends)
+    index = ops.span_index(starts, ends, T, dev)
+    S = index.n_spans
+    rows = (S + 63) // 64 * 64
+    X = torch.randn(T, W, device=dev).to(torch.bfloat16)
+    dR = torch.randn(rows, 4 * W, device=dev).to(torch.bfloat16)
+    fwd_bytes = S * (4 * W * 2 + W) + T * W * 2
+    bwd_bytes = S * 4 * W * 2 + S * W + T * W * 2
+    print(f"span_pool (T={T}, W={W}, bf16, S={S} spans of 1..3 tokens):")
+
+    Rf, which = hip.span_pool_fwd(X, index.starts, index.ends, rows)
+    fwd = _alternate({
+        "fused": lambda: hip.span_pool_fwd(X, index.starts, index.ends, rows),
+        "composed": lambda: ref.span_pool(X, index.starts, index.ends, 3),
+    })
+    for name, (med, mn) in fwd.items():
+        print(f"  fwd {name:9s} median {med:8.3f} ms  min {mn:8.3f} ms  "
+              f"{fwd_bytes / med / 1e9:8.3f} TB/s of the {fwd_bytes} floor bytes")
+
+    x = X.clone().requires_grad_(True)
+    Rc, _ = ref.span_pool(x, index.starts, index.ends, 3)
+
+    def composed_bwd():
+        return torch.autograd.grad(Rc, x, dR[:S], retain_graph=True)[0]
+
+    def fused_bwd():
+        return hip.span_pool_bwd(dR, which, index.starts, index.ends,
+                                 index.tok_offsets, index.tok_spans)
+
+    diff = (fused_bwd().float() - composed_bwd().float()).abs().max().item()
+    bwd = _alternate({"fused": fused_bwd, "composed": composed_bwd})
+    for name, (med, mn) in bwd.items():
+        print(f"  bwd {name:9s} median {med:8.3f} ms  min {mn:8.3f} ms  "
+              f"{bwd_bytes / med / 1e9:8.3f} TB/s of the {bwd_bytes} floor bytes")
+    print(f"  max |R fused - composed| = "
+          f"{(Rf[:S].float() - Rc.float()).abs().max().item():.3e}, "
+          f"max |dX fused - composed| = {diff:.3e}")
+    del Rc, x, Rf
+
+    head = SpancatReducerHead(W, W, 4).to(dev).to(torch.bfloat16)
+    target = (torch.rand(S, 4, device=dev) < 0.05).float()
+    t2v = X.clone().requires_grad_(True)
+
+    def step(span_pool, mixer):
+        def run():
+            os.environ["SRX_SPAN_POOL"] = span_pool
+            os.environ["SRX_MIXER"] = mixer
+            scores = head(t2v, index)
+            loss = torch.nn.functional.binary_cross_entropy_with_logits(
+                scores.float(), target, reduction="sum") / S
+            loss.backward()
+            t2v.grad = None
+            head.zero_grad(set_to_none=True)
+        return run
+
+    routes = _alternate({"fused": step("fused", ""),
+                         "composed": step("composed", "composed")}, iters=10, warmup=3)
+    os.environ.pop("SRX_SPAN_POOL")
+    os.environ.pop("SRX_MIXER")
+    for name, (med, mn) in routes.items():
+        print(f"  head + loss fwd+bwd {name:9s} median {med:8.3f} ms  min {mn:8.3f} ms")
+
+
 ALL = {"mwe": bench_mwe, "dpre": bench_dpre, "ce": bench_ce, "mixer": bench_mixer,
        "mwe_dw": bench_mwe_dw,
        "floret": bench_floret, "vecloss": bench_vecloss,
-       "most_similar": bench_most_similar,
+       "most_similar": bench_most_similar, "span_pool": bench_span_pool,
        "gpustate": bench_gpustate, "attn": bench_attn,
        "static_vectors": bench_static_vectors,
        "hashembed": bench_hashembed}
