@@ -213,6 +213,36 @@ def make_textcat_reduce_model(tok2vec: ModelSpec,
     return spec
 
 
+def _textcat_bow_spec(name: str, ngram_size: int, length: int) -> ModelSpec:
+    ngram_size, length = int(ngram_size), int(length)
+    if ngram_size < 1:
+        raise ValueError(f"{name}: ngram_size must be >= 1, got {ngram_size}")
+    if length < 1 or length & (length - 1):
+        raise ValueError(
+            f"{name}: length must be a power of two (the hashed rows are "
+            f"masked with length - 1), got length = {length}")
+    # no tok2vec and no width: a bag of hashed token n-grams through Thinc's
+    # SparseLinear (ops.sparse_linear); TextcatPipe builds the head
+    spec = ModelSpec(lambda: None, width=None, kind="textcat")
+    spec.bow = {"ngram_size": ngram_size, "length": length}
+    return spec
+
+
+@registry.architectures("spacy.TextCatBOW.v2")
+def make_textcat_bow_v2(exclusive_classes: bool = True, ngram_size: int = 1,
+                        no_output_layer: bool = False, nO: Optional[int] = None):
+    """spaCy's efficiency-mode text classifier.  `no_output_layer` changes
+    nothing here: the softmax / sigmoid lives in the loss and in prediction."""
+    return _textcat_bow_spec("spacy.TextCatBOW.v2", ngram_size, 262144)
+
+
+@registry.architectures("spacy.TextCatBOW.v3")
+def make_textcat_bow_v3(exclusive_classes: bool = True, ngram_size: int = 1,
+                        no_output_layer: bool = False, length: int = 262144,
+                        nO: Optional[int] = None):
+    return _textcat_bow_spec("spacy.TextCatBOW.v3", ngram_size, length)
+
+
 @registry.layers("spacy.mean_max_reducer.v1")
 def make_mean_max_reducer(hidden_size: int = 128):
     """spaCy's span reducer: last | first | mean | max over the span's

@@ -740,6 +740,136 @@ def span_pool(X: torch.Tensor, index: SpanIndex, pad_rows: int = 1) -> torch.Ten
     return R
 
 
+# ------------------------------------------------ SparseLinear (TextCatBOW)
+# sparse_linear kernels (srx_sparselinear.hip.h) against the composed path
+# (torch_ref.sparse_linear over ngram_buckets: an [2 nnz, nO] gather, a
+# segment sum, index_add_ atomics backward).  Same rule as span_pool: fused
+# by default only where tools/kbench.py sparse_linear measured it not slower,
+# forward and backward both (docs/KERNELS.md, "SparseLinear");
+# SRX_SPARSE_LINEAR=fused / composed overrides.
+# Measured (50k docs of 20 tokens, G = 3, L = 262144, bf16): nO = 4 forward
+# 0.072 ms against 1.949 ms, backward 0.700 ms against 2.742 ms; nO = 32
+# forward 0.146 ms against 3.260 ms, backward 1.019 ms against 3.172 ms.
+SPARSE_LINEAR_FUSED_DEFAULT = True
+SPARSE_LINEAR_MAX_NO = 128
+SPARSE_LINEAR_MAX_NGRAM = 4
+SPARSE_LINEAR_MAX_LENGTH = 1 << 24
+
+
+def _check_sparse_linear(ids, offsets, ngram_size, length) -> None:
+    if ids.dim() != 1 or ids.dtype != torch.int64:
+        raise ValueError("sparse_linear: ids must be int64 [T]")
+    if offsets.dim() != 1 or offsets.numel() < 1 or offsets.dtype != torch.int32:
+        raise ValueError("sparse_linear: offsets must be int32 [D + 1]")
+    if int(ngram_size) < 1:
+        raise ValueError("sparse_linear: ngram_size must be >= 1")
+    if length < 1 or length & (length - 1):
+        raise ValueError("sparse_linear: the table length must be a power of two")
+
+
+def ngram_buckets(ids: torch.Tensor, offsets: torch.Tensor, ngram_size: int,
+                  length: int) -> torch.Tensor:
+    """int32 [nnz, 2]: the two table rows (b0, b1) of every token n-gram of
+    every doc, n = 1..ngram_size, doc-major, then n, then position.  ids are
+    the uint64 token keys bit-cast to int64 [T], offsets int32 [D + 1].  On a
+    GPU with ngram_size <= 4 this is ngram_buckets_kernel (one sync for the
+    row count), else the host function."""
+    _check_sparse_linear(ids, offsets, ngram_size, int(length))
+    if (ids.is_cuda and _want_hip(ids) and ngram_size <= SPARSE_LINEAR_MAX_NGRAM
+            and length <= SPARSE_LINEAR_MAX_LENGTH
+            and 2 * ngram_size * ids.numel() < 2 ** 31):
+        occ = torch.zeros(offsets.numel(), dtype=torch.int64, device=ids.device)
+        torch.cumsum(ref.ngram_counts(offsets, ngram_size), 0, out=occ[1:])
+        return hip_ext().ngram_buckets(ids.contiguous(), offsets.contiguous(), occ,
+                                       int(occ[-1]), int(ngram_size), int(length))
+    return ref.ngram_buckets(ids, offsets, ngram_size, length)
+
+
+def sparse_linear_available(ids: torch.Tensor, weight: torch.Tensor,
+                            ngram_size: int) -> bool:
+    """The kernels take a contiguous bf16 or fp32 weight [L, nO] on the GPU
+    with nO <= 128 and L a power of two <= 2^24, ngram_size <= 4 and
+    2 * ngram_size * T < 2^31."""
+    return (
+        weight.is_cuda and ids.is_cuda and weight.dim() == 2
+        and weight.dtype in (torch.bfloat16, torch.float32)
+        and weight.is_contiguous()
+        and 0 < weight.shape[1] <= SPARSE_LINEAR_MAX_NO
+        and weight.shape[0] <= SPARSE_LINEAR_MAX_LENGTH
+        and 1 <= ngram_size <= SPARSE_LINEAR_MAX_NGRAM
+        and 2 * ngram_size * ids.numel() < 2 ** 31
+        and hip_ext() is not None
+    )
+
+
+def _sparse_linear_fused(ids, weight, ngram_size) -> bool:
+    mode = os.environ.get("SRX_SPARSE_LINEAR", "")
+    if mode not in ("", "fused", "composed"):
+        raise ValueError(
+            f"SRX_SPARSE_LINEAR={mode!r}: expected 'fused' or 'composed'")
+    if mode == "composed" or not weight.is_cuda:
+        return False
+    _want_hip(weight)  # a GPU run without the extension is an error, as elsewhere
+    if not sparse_linear_available(ids, weight, ngram_size):
+        return False
+    return mode == "fused" or SPARSE_LINEAR_FUSED_DEFAULT
+
+
+class _SparseLinear(torch.autograd.Function):
+    """Forward: one launch, hashing in registers.  Backward: the keys kernel,
+    one sort, the chunked segmented reduce and its fix-up; no atomics."""
+
+    @staticmethod
+    def forward(ctx, ids, offsets, weight, bias, ngram_size, sub_wave, max_blocks):
+        ctx.save_for_backward(ids, offsets)
+        ctx.args = (int(ngram_size), weight.shape[0], weight.dtype, bias.dtype,
+                    int(max_blocks))
+        return hip_ext().sparse_linear_fwd(ids, offsets, weight.detach(),
+                                           bias.detach().float().contiguous(),
+                                           int(ngram_size), int(sub_wave),
+                                           int(max_blocks))
+
+    @staticmethod
+    def backward(ctx, dS):
+        ids, offsets = ctx.saved_tensors
+        G, L, wdtype, bdtype, max_blocks = ctx.args
+        dS = dS.float().contiguous()
+        dW = dB = None
+        if ctx.needs_input_grad[2]:
+            keys = hip_ext().sparse_linear_keys(ids, offsets, G, L)
+            dW = hip_ext().sparse_linear_bwd(torch.sort(keys).values, dS, L,
+                                             wdtype == torch.bfloat16, max_blocks)
+        if ctx.needs_input_grad[3]:
+            dB = dS.sum(0).to(bdtype)
+        return None, None, dW, dB, None, None, None
+
+
+def sparse_linear(ids: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
+                  bias: torch.Tensor, ngram_size: int = 1, *, sub_wave: int = 0,
+                  max_blocks: int = 0) -> torch.Tensor:
+    """Thinc's SparseLinear over hashed token n-grams, the model of spaCy's
+    TextCatBOW.  ids: the docs' uint64 token keys bit-cast to int64 [T];
+    offsets int32 [D + 1]; weight [L, nO] with L a power of two; bias [nO].
+    For every doc, n in 1..ngram_size and position i: key = murmur2_64a of
+    the n ids (seed 0), (b0, b1) = the first two murmur3 lanes of the key
+    masked to L - 1, and scores[d] = bias + sum (weight[b0] + weight[b1]),
+    fp32 [D, nO], with autograd to weight and bias (dWeight rounded once).
+    On a GPU (sparse_linear_available) the forward is one HIP launch and the
+    backward is atomic-free and bit-reproducible; everything else takes
+    torch_ref.sparse_linear.  SRX_SPARSE_LINEAR=fused|composed overrides the
+    default.  sub_wave (0 / 8 / 16 / 32 / 64 lanes per doc) pins the
+    forward's summation order, max_blocks > 0 caps the grids; both are for
+    tests and measurements."""
+    _check_sparse_linear(ids, offsets, ngram_size, weight.shape[0])
+    if weight.dim() != 2 or bias.shape != (weight.shape[1],):
+        raise ValueError("sparse_linear: weight must be [L, nO] and bias [nO]")
+    if _sparse_linear_fused(ids, weight, ngram_size):
+        return _SparseLinear.apply(ids.contiguous(), offsets.contiguous(), weight,
+                                   bias, ngram_size, sub_wave, max_blocks)
+    buckets = ngram_buckets(ids, offsets, ngram_size, weight.shape[0])
+    return ref.sparse_linear(ids, offsets, weight, bias, ngram_size, buckets)
+
+
 # ---------------------------------------------------- vectors most_similar
 # Cosine top-n over the vectors table (srx_vecsim.hip.h, in the extension
 # module _srx_hip_vecsim) against the composed path

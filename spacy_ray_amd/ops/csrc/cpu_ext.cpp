@@ -165,6 +165,48 @@ static py::tuple dedupe_keys(py::array_t<uint64_t, py::array::c_style | py::arra
   return py::make_tuple(inverse, first_arr);
 }
 
+// TextCatBOW / SparseLinear features (the oracle of the device hash in
+// ops/kernels/srx_sparselinear.hip.h): for every doc, n in 1..ngram_size and
+// position i with i + n <= len, key = murmur2_64a(ids[i .. i + n), 8 n bytes,
+// seed 0), h = murmur3_hash4_u64(key, 0), row (h[0] & (length - 1),
+// h[1] & (length - 1)).  int32 [nnz, 2], doc-major, then n, then position.
+static py::array_t<int32_t> ngram_buckets(
+    py::array_t<uint64_t, py::array::c_style | py::array::forcecast> ids,
+    py::array_t<int32_t, py::array::c_style | py::array::forcecast> offsets,
+    int ngram_size, int64_t length) {
+  if (ngram_size < 1) throw std::invalid_argument("ngram_buckets: ngram_size must be >= 1");
+  if (length < 1 || length > (int64_t(1) << 24) || (length & (length - 1)))
+    throw std::invalid_argument("ngram_buckets: length must be a power of two <= 2^24");
+  if (ids.ndim() != 1 || offsets.ndim() != 1 || offsets.shape(0) < 1)
+    throw std::invalid_argument("ngram_buckets: ids [T], offsets [D + 1]");
+  const int64_t T = ids.shape(0), D = offsets.shape(0) - 1;
+  const uint64_t* id = ids.data();
+  const int32_t* off = offsets.data();
+  int64_t nnz = 0;
+  for (int64_t d = 0; d < D; d++) {
+    if (off[d] < 0 || off[d + 1] < off[d] || off[d + 1] > T)
+      throw std::invalid_argument("ngram_buckets: offsets must ascend within [0, T]");
+    const int64_t len = off[d + 1] - off[d];
+    for (int n = 1; n <= ngram_size && n <= len; n++) nnz += len - n + 1;
+  }
+  if (nnz >= (int64_t(1) << 30))
+    throw std::overflow_error("ngram_buckets: too many n-grams; split the batch");
+  py::array_t<int32_t> out({(py::ssize_t)nnz, (py::ssize_t)2});
+  int32_t* o = out.mutable_data();
+  const uint32_t mask = (uint32_t)(length - 1);
+  for (int64_t d = 0; d < D; d++) {
+    const int64_t beg = off[d], len = off[d + 1] - off[d];
+    for (int n = 1; n <= ngram_size && n <= len; n++)
+      for (int64_t i = 0; i + n <= len; i++) {
+        uint32_t h[4];
+        srx::murmur3_hash4_u64(srx::murmur2_64a(id + beg + i, 8 * n, 0), 0u, h);
+        *o++ = (int32_t)(h[0] & mask);
+        *o++ = (int32_t)(h[1] & mask);
+      }
+  }
+  return out;
+}
+
 void init_transitions(py::module_& m);  // transitions.cpp
 
 PYBIND11_MODULE(_srx_cpu, m) {
@@ -195,5 +237,8 @@ PYBIND11_MODULE(_srx_cpu, m) {
         "floret n-gram table rows of each word as a CSR (offsets, idx)");
   m.def("dedupe_keys", &dedupe_keys, py::arg("keys"), py::arg("skip_key"),
         "distinct uint64 keys in first-occurrence order: (inverse, first)");
+  m.def("ngram_buckets", &ngram_buckets, py::arg("ids"), py::arg("offsets"),
+        py::arg("ngram_size"), py::arg("length"),
+        "hashed n-gram table rows (TextCatBOW): int32 [nnz, 2]");
   init_transitions(m);
 }

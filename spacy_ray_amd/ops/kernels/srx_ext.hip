@@ -21,6 +21,7 @@
 #include "srx_floret.hip.h"
 #include "srx_vecloss.hip.h"
 #include "srx_spanpool.hip.h"
+#include "srx_sparselinear.hip.h"
 #include "srx_activations.hip.h"
 #include "srx_attn.hip.h"
 
@@ -2015,6 +2016,183 @@ at::Tensor span_pool_bwd(at::Tensor dR, at::Tensor which, at::Tensor starts,
 }
 #undef SRX_SPANPOOL_DISPATCH
 
+// ------------------------------------------------- SparseLinear (TextCatBOW)
+// see srx_sparselinear.hip.h.  ids int64 [T], offsets int32 [D + 1], weight
+// bf16 / fp32 [L, nO], L a power of two <= 2^24, nO <= 128, G <= 4.
+namespace spl {
+
+inline dim3 grid_for(long blocks, long max_blocks) {
+  long cap = 8L * at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  if (max_blocks > 0) cap = max_blocks;
+  return dim3((unsigned)std::max<long>(1, std::min<long>(blocks, cap)));
+}
+
+inline int pow2_ceil(long x) {
+  int p = 1;
+  while (p < x) p <<= 1;
+  return p;
+}
+
+// -> (T, D); 2 G T < 2^31 keeps every entry index in int32 range
+inline std::pair<long, long> check_docs(const at::Tensor& ids, const at::Tensor& offsets,
+                                        long G, long L) {
+  check_dev(ids);
+  check_dev(offsets);
+  TORCH_CHECK(ids.scalar_type() == at::kLong && ids.dim() == 1,
+              "sparse_linear: ids must be int64 [T]");
+  TORCH_CHECK(offsets.scalar_type() == at::kInt && offsets.dim() == 1 &&
+                  offsets.numel() >= 1,
+              "sparse_linear: offsets must be int32 [D + 1]");
+  TORCH_CHECK(G >= 1 && G <= 4, "sparse_linear: ngram_size must be in 1..4");
+  TORCH_CHECK(L >= 1 && L <= (1L << 24) && (L & (L - 1)) == 0,
+              "sparse_linear: length must be a power of two <= 2^24");
+  const long T = ids.numel(), D = offsets.numel() - 1;
+  TORCH_CHECK(2 * G * T < (1L << 31) && D < (1L << 31),
+              "sparse_linear: 2 * ngram_size * T and D must be < 2^31");
+  return {T, D};
+}
+
+}  // namespace spl
+
+// int32 [nnz, 2]; occ_offsets int64 [D + 1] = prefix sum of the docs'
+// occurrence counts, nnz its last element
+at::Tensor ngram_buckets(at::Tensor ids, at::Tensor offsets, at::Tensor occ_offsets,
+                         long nnz, long G, long L) {
+  const auto [T, D] = spl::check_docs(ids, offsets, G, L);
+  check_dev(occ_offsets);
+  TORCH_CHECK(occ_offsets.scalar_type() == at::kLong && occ_offsets.dim() == 1 &&
+                  occ_offsets.numel() == D + 1 && nnz >= 0 && nnz < (1L << 30),
+              "ngram_buckets: occ_offsets must be int64 [D + 1], nnz < 2^30");
+  auto out = at::empty({nnz, 2}, offsets.options());
+  if (nnz == 0 || T == 0) return out;
+  const dim3 grid = spl::grid_for((T + SRX_SPL_THREADS - 1) / SRX_SPL_THREADS, 0);
+  hipLaunchKernelGGL(ngram_buckets_kernel, grid, dim3(SRX_SPL_THREADS), 0,
+                     at::cuda::getCurrentCUDAStream(), ids.data_ptr<int64_t>(),
+                     offsets.data_ptr<int>(), occ_offsets.data_ptr<int64_t>(),
+                     out.data_ptr<int>(), (int)D, (int)T, (int)G, (uint32_t)(L - 1),
+                     nnz);
+  return out;
+}
+
+// scores fp32 [D, nO].  sub_wave: 0 = from the mean occurrences per doc, or
+// 8 / 16 / 32 / 64 (raised to the lanes a row needs); max_blocks > 0 caps
+// the grid.
+at::Tensor sparse_linear_fwd(at::Tensor ids, at::Tensor offsets, at::Tensor weight,
+                             at::Tensor bias, long G, long sub_wave, long max_blocks) {
+  check_dev(weight);
+  check_dev(bias);
+  TORCH_CHECK(weight.dim() == 2 && (weight.scalar_type() == at::kBFloat16 ||
+                                    weight.scalar_type() == at::kFloat),
+              "sparse_linear_fwd: weight must be bf16 or fp32 [L, nO]");
+  const long L = weight.size(0), nO = weight.size(1);
+  const auto [T, D] = spl::check_docs(ids, offsets, G, L);
+  TORCH_CHECK(nO >= 1 && nO <= 128, "sparse_linear_fwd: nO must be in 1..128");
+  TORCH_CHECK(bias.scalar_type() == at::kFloat && bias.dim() == 1 && bias.numel() == nO,
+              "sparse_linear_fwd: bias must be fp32 [nO]");
+  TORCH_CHECK(aligned16(weight.data_ptr()), "sparse_linear_fwd: weight not 16-byte aligned");
+  TORCH_CHECK(sub_wave == 0 || sub_wave == 8 || sub_wave == 16 || sub_wave == 32 ||
+                  sub_wave == 64,
+              "sparse_linear_fwd: sub_wave must be 0, 8, 16, 32 or 64");
+  auto scores = at::empty({D, nO}, weight.options().dtype(at::kFloat));
+  if (D == 0) return scores;
+  const bool bf16 = weight.scalar_type() == at::kBFloat16;
+  int C = bf16 ? 8 : 4;
+  while (nO % C) C >>= 1;
+  const int CL = std::min(spl::pow2_ceil(nO / C), 64);
+  long sw = sub_wave;
+  if (sw == 0) {  // occurrences per doc ~ G tokens-per-doc, CL lanes each
+    const long per_doc = std::max<long>(1, G * T / D) * CL;
+    sw = std::min<long>(64, std::max<long>(8, spl::pow2_ceil(per_doc)));
+  }
+  sw = std::max<long>(sw, CL);
+  const long per_block = (SRX_SPL_THREADS / SRX_WAVE) * (SRX_WAVE / sw);
+  const dim3 grid = spl::grid_for((D + per_block - 1) / per_block, max_blocks);
+  auto stream = at::cuda::getCurrentCUDAStream();
+#define SRX_SPL_FWD(TT, SW, CC)                                                \
+  hipLaunchKernelGGL((sparse_linear_fwd_kernel<TT, SW, CC>), grid,             \
+                     dim3(SRX_SPL_THREADS), 0, stream, ids.data_ptr<int64_t>(),\
+                     offsets.data_ptr<int>(), (const TT*)weight.data_ptr(),    \
+                     bias.data_ptr<float>(), scores.data_ptr<float>(), (int)D, \
+                     (int)T, (int)G, (int)nO, (uint32_t)(L - 1), CL)
+#define SRX_SPL_FWD_SW(TT, CC)                                                 \
+  if (sw == 8) { SRX_SPL_FWD(TT, 8, CC); }                                     \
+  else if (sw == 16) { SRX_SPL_FWD(TT, 16, CC); }                              \
+  else if (sw == 32) { SRX_SPL_FWD(TT, 32, CC); }                              \
+  else { SRX_SPL_FWD(TT, 64, CC); }
+  if (bf16) {
+    if (C == 8) { SRX_SPL_FWD_SW(bf16_t, 8) }
+    else if (C == 4) { SRX_SPL_FWD_SW(bf16_t, 4) }
+    else if (C == 2) { SRX_SPL_FWD_SW(bf16_t, 2) }
+    else { SRX_SPL_FWD_SW(bf16_t, 1) }
+  } else {
+    if (C == 4) { SRX_SPL_FWD_SW(float, 4) }
+    else if (C == 2) { SRX_SPL_FWD_SW(float, 2) }
+    else { SRX_SPL_FWD_SW(float, 1) }
+  }
+#undef SRX_SPL_FWD_SW
+#undef SRX_SPL_FWD
+  return scores;
+}
+
+// int64 [2 G T]: (bucket << 32) | doc per entry, the sentinel where an
+// n-gram would cross its doc's end
+at::Tensor sparse_linear_keys(at::Tensor ids, at::Tensor offsets, long G, long L) {
+  const auto [T, D] = spl::check_docs(ids, offsets, G, L);
+  auto keys = at::empty({2 * G * T}, ids.options());
+  if (T == 0) return keys;
+  const dim3 grid = spl::grid_for((T + SRX_SPL_THREADS - 1) / SRX_SPL_THREADS, 0);
+  hipLaunchKernelGGL(sparse_linear_keys_kernel, grid, dim3(SRX_SPL_THREADS), 0,
+                     at::cuda::getCurrentCUDAStream(), ids.data_ptr<int64_t>(),
+                     offsets.data_ptr<int>(), keys.data_ptr<int64_t>(), (int)D,
+                     (int)T, (int)G, (uint32_t)(L - 1));
+  return keys;
+}
+
+// dWeight [L, nO] (bf16: as_bf16) from the SORTED keys and dScores fp32 [D, nO]
+at::Tensor sparse_linear_bwd(at::Tensor sorted, at::Tensor dS, long L, bool as_bf16,
+                             long max_blocks) {
+  check_dev(sorted);
+  check_dev(dS);
+  TORCH_CHECK(sorted.scalar_type() == at::kLong && sorted.dim() == 1,
+              "sparse_linear_bwd: sorted must be int64 [N]");
+  TORCH_CHECK(dS.scalar_type() == at::kFloat && dS.dim() == 2,
+              "sparse_linear_bwd: dScores must be fp32 [D, nO]");
+  const long N = sorted.numel(), D = dS.size(0), nO = dS.size(1);
+  TORCH_CHECK(nO >= 1 && nO <= 128, "sparse_linear_bwd: nO must be in 1..128");
+  TORCH_CHECK(L >= 1 && L <= (1L << 24) && N < (1L << 31) && D < (1L << 31),
+              "sparse_linear_bwd: L <= 2^24, N and D < 2^31");
+  TORCH_CHECK(aligned16(dS.data_ptr()), "sparse_linear_bwd: dScores not 16-byte aligned");
+  auto dW = at::zeros({L, nO}, dS.options().dtype(as_bf16 ? at::kBFloat16 : at::kFloat));
+  if (N == 0 || D == 0) return dW;
+  const long n_chunks = (N + SRX_SPL_CHUNK - 1) / SRX_SPL_CHUNK;
+  auto cbucket = at::empty({n_chunks, 2}, dS.options().dtype(at::kInt));
+  auto crow = at::empty({n_chunks, 2, nO}, dS.options());
+  const long wpb = SRX_SPL_THREADS / SRX_WAVE;
+  const dim3 grid = spl::grid_for((n_chunks + wpb - 1) / wpb, max_blocks);
+  const dim3 fgrid = spl::grid_for(
+      (2 * n_chunks * nO + SRX_SPL_THREADS - 1) / SRX_SPL_THREADS, max_blocks);
+  const bool vec = nO % 4 == 0;
+  auto stream = at::cuda::getCurrentCUDAStream();
+#define SRX_SPL_BWD(TT, VEC)                                                   \
+  hipLaunchKernelGGL((sparse_linear_bwd_kernel<TT, VEC>), grid,                \
+                     dim3(SRX_SPL_THREADS), 0, stream,                         \
+                     sorted.data_ptr<int64_t>(), dS.data_ptr<float>(),         \
+                     (TT*)dW.data_ptr(), cbucket.data_ptr<int>(),              \
+                     crow.data_ptr<float>(), N, n_chunks, (int)D, (int)L,      \
+                     (int)nO);                                                 \
+  hipLaunchKernelGGL((sparse_linear_fixup_kernel<TT>), fgrid,                  \
+                     dim3(SRX_SPL_THREADS), 0, stream, cbucket.data_ptr<int>(),\
+                     crow.data_ptr<float>(), (TT*)dW.data_ptr(), 2 * n_chunks, \
+                     (int)L, (int)nO)
+  if (as_bf16) {
+    if (vec) { SRX_SPL_BWD(bf16_t, true); } else { SRX_SPL_BWD(bf16_t, false); }
+  } else {
+    if (vec) { SRX_SPL_BWD(float, true); } else { SRX_SPL_BWD(float, false); }
+  }
+#undef SRX_SPL_BWD
+  return dW;
+}
+
 // --------------------------------------------- fused transition step (C++)
 // One python call per transition step: state scorer kernel + upper GEMM +
 // on-device action selection, with a C++ autograd node so the per-step
@@ -2186,6 +2364,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("span_pool_bwd", &span_pool_bwd, py::arg("dR"), py::arg("which"),
         py::arg("starts"), py::arg("ends"), py::arg("tok_offsets"),
         py::arg("tok_spans"));
+  m.def("ngram_buckets", &ngram_buckets, py::arg("ids"), py::arg("offsets"),
+        py::arg("occ_offsets"), py::arg("nnz"), py::arg("ngram_size"),
+        py::arg("length"));
+  m.def("sparse_linear_fwd", &sparse_linear_fwd, py::arg("ids"), py::arg("offsets"),
+        py::arg("weight"), py::arg("bias"), py::arg("ngram_size"),
+        py::arg("sub_wave") = 0, py::arg("max_blocks") = 0);
+  m.def("sparse_linear_keys", &sparse_linear_keys, py::arg("ids"),
+        py::arg("offsets"), py::arg("ngram_size"), py::arg("length"));
+  m.def("sparse_linear_bwd", &sparse_linear_bwd, py::arg("sorted"),
+        py::arg("dScores"), py::arg("length"), py::arg("as_bf16"),
+        py::arg("max_blocks") = 0);
   m.def("fused_step",&fusedstep::fused_step);
   m.def("fused_entries_take", &fusedstep::fused_entries_take);
   m.def("transition_ce", &transition_ce, py::arg("scores"), py::arg("gold"),

@@ -179,6 +179,47 @@ def span_pool(X: torch.Tensor, starts: torch.Tensor, ends: torch.Tensor,
     return torch.cat(Rs), torch.cat(whichs)
 
 
+def ngram_counts(offsets: torch.Tensor, ngram_size: int) -> torch.Tensor:
+    """int64 [D]: n-gram occurrences per doc, sum_n max(0, len - n + 1)."""
+    lens = (offsets[1:] - offsets[:-1]).long()
+    return sum((lens - n + 1).clamp(min=0) for n in range(1, int(ngram_size) + 1))
+
+
+def ngram_buckets(ids: torch.Tensor, offsets: torch.Tensor, ngram_size: int,
+                  length: int) -> torch.Tensor:
+    """int32 [nnz, 2] on ids' device: the two table rows of every token
+    n-gram, doc-major, then n, then position (the host implementation,
+    _srx_cpu.ngram_buckets)."""
+    from spacy_ray_amd import _srx_cpu
+
+    out = _srx_cpu.ngram_buckets(ids.detach().cpu().numpy().view(np.uint64),
+                                 offsets.detach().cpu().numpy().astype(np.int32),
+                                 int(ngram_size), int(length))
+    return torch.from_numpy(out).to(ids.device)
+
+
+def sparse_linear(ids: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor,
+                  bias: torch.Tensor, ngram_size: int,
+                  buckets: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Thinc's SparseLinear over hashed token n-grams (spaCy's TextCatBOW):
+    scores[d] = bias + sum over the doc's n-gram occurrences of weight[b0] +
+    weight[b1], fp32 (fp64 for an fp64 weight) [D, nO].  An index_select and
+    a segment sum; autograd reaches weight through index_add_.  `buckets`
+    [nnz, 2] defaults to ngram_buckets(...)."""
+    L, nO = weight.shape
+    D = offsets.numel() - 1
+    if buckets is None:
+        buckets = ngram_buckets(ids, offsets, ngram_size, L)
+    acc = torch.float64 if weight.dtype == torch.float64 else torch.float32
+    doc_of = torch.repeat_interleave(
+        torch.arange(D, device=weight.device), ngram_counts(offsets, ngram_size),
+        output_size=buckets.shape[0])
+    # cast first: the gradient is then summed in fp32 and rounded once
+    rows = weight.to(acc).index_select(0, buckets.reshape(-1).long())
+    scores = bias.to(acc).expand(D, nO).clone()
+    return scores.index_add_(0, doc_of.repeat_interleave(2), rows)
+
+
 def vectors_loss(pred: torch.Tensor, table: torch.Tensor, rows: torch.Tensor,
                  loss: str = "cosine", scale: float = 1.0):
     """pred [N, nM], table [V, >= nM], rows [N] int -> (row_loss [N] in the

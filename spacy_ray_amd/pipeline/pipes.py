@@ -1099,6 +1099,22 @@ class TextcatHead(nn.Module):
         return linear_cdw(X, self.output.weight, self.output.bias)
 
 
+class TextcatBowHead(nn.Module):
+    """spaCy's TextCatBOW: Thinc's SparseLinear over hashed token n-grams
+    (ops.sparse_linear).  weight [length, n_cats] starts at zero as in Thinc."""
+
+    def __init__(self, length: int, n_cats: int, ngram_size: int):
+        super().__init__()
+        self.ngram_size = int(ngram_size)
+        self.weight = nn.Parameter(torch.zeros(int(length), n_cats))
+        self.bias = nn.Parameter(torch.zeros(n_cats))
+
+    def forward(self, ids, offsets):
+        from spacy_ray_amd.ops.api import sparse_linear
+
+        return sparse_linear(ids, offsets, self.weight, self.bias, self.ngram_size)
+
+
 class TextcatPipe(TrainablePipe):
     """Doc-level classification over mean-pooled tok2vec (the reference is
     a generic spaCy trainer — `spacy ray train` accepts textcat configs,
@@ -1123,6 +1139,17 @@ class TextcatPipe(TrainablePipe):
         self.exclusive = exclusive_classes
         self.labels: List[str] = []
         self.label2id: Dict[str, int] = {}
+        # spacy.TextCatBOW: {"ngram_size", "length"}; no tok2vec at all, so
+        # this instance listens to nothing and ignores t2v
+        self.bow = getattr(spec, "bow", None)
+        if self.bow is not None:
+            self.listens_to = None
+
+    def _build_head(self, device):
+        n = max(1, len(self.labels))
+        if self.bow is not None:
+            return TextcatBowHead(self.bow["length"], n, self.bow["ngram_size"]).to(device)
+        return TextcatHead(self.width, n).to(device)
 
     def initialize(self, examples, device) -> None:
         if not self.labels:
@@ -1134,8 +1161,10 @@ class TextcatPipe(TrainablePipe):
             self.label2id = {t: i for i, t in enumerate(self.labels)}
         self.cfg["labels"] = self.labels
         self.cfg["exclusive"] = self.exclusive
+        if self.bow is not None:
+            self.cfg.update(self.bow)
         if self.module is None:
-            self.module = TextcatHead(self.width, max(1, len(self.labels))).to(device)
+            self.module = self._build_head(device)
         self._attach_embedded(device)
 
     def load_cfg(self, cfg, device) -> None:
@@ -1143,13 +1172,37 @@ class TextcatPipe(TrainablePipe):
         self.labels = list(cfg.get("labels", []))
         self.label2id = {t: i for i, t in enumerate(self.labels)}
         self.exclusive = bool(cfg.get("exclusive", True))
+        if self.bow is not None:  # rebuild the head that was saved
+            self.bow = {k: int(cfg.get(k, self.bow[k])) for k in ("ngram_size", "length")}
         if self.module is None:
-            self.module = TextcatHead(self.width, max(1, len(self.labels))).to(device)
+            self.module = self._build_head(device)
         self._attach_embedded(device)
+
+    def _bow_inputs(self, batch, docs):
+        """(ids int64 [T], offsets int32 [D + 1]) of the real docs (the
+        TokenBatch pad pseudo-doc is left out), uploaded once per batch."""
+        key = ("bow_keys", "ORTH")
+        if batch is not None and key in batch.staged:
+            return batch.staged[key]
+        from spacy_ray_amd.utils.pinned import to_device
+
+        docs = batch.docs if batch is not None else docs
+        parts = [d.get_vector_keys("ORTH") for d in docs]
+        ids = (np.concatenate(parts) if parts
+               else np.zeros(0, dtype=np.uint64)).astype(np.uint64, copy=False)
+        offsets = np.zeros(len(docs) + 1, dtype=np.int32)
+        np.cumsum([len(p) for p in parts], out=offsets[1:])
+        device = self.module.weight.device
+        staged = (to_device(ids.view(np.int64), device), to_device(offsets, device))
+        if batch is not None:
+            batch.staged[key] = staged
+        return staged
 
     def _doc_scores(self, t2v, batch, docs):
         from spacy_ray_amd.ops import api as _ops
 
+        if self.bow is not None:
+            return self.module(*self._bow_inputs(batch, docs))
         if batch is not None:
             lengths, total = batch.lengths, batch.n_tokens
         else:

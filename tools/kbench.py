@@ -825,7 +825,76 @@ def bench_span_pool():
         print(f"  head + loss fwd+bwd {name:9s} median {med:8.3f} ms  min {mn:8.3f} ms")
 
 
-ALL = {"mwe": bench_mwe, "dpre": bench_dpre, "ce": bench_ce, "mixer": bench_mixer,
+def bench_sparse_linear():
+    """sparse_linear (srx_sparselinear.hip.h) against the composed path
+    (ops.ngram_buckets + torch_ref.sparse_linear and its autograd backward)
+    on the bench corpus's shape: 50,000 docs of 20 tokens, Zipf ids over 5000
+    types, G = 3, L = 262144, bf16, nO = 4 and 32.  Whole calls: the fused
+    backward includes the keys kernel, the sort, the dWeight zero fill and
+    the fix-up; the sort is also timed alone."""
+    import numpy as np
+
+    from spacy_ray_amd.ops import api as ops
+    from spacy_ray_amd.ops import torch_ref as ref
+
+    D, doc, G, L = 50000, 20, 3, 262144
+    rng = np.random.RandomState(0)
+    p = 1.0 / np.arange(1, 5001)
+    types = rng.randint(1, 2 ** 62, 5000).astype(np.int64)
+    ids = torch.from_numpy(types[rng.choice(5000, D * doc, p=p / p.sum())]).to(dev)
+    offsets = torch.arange(0, D * doc + 1, doc, dtype=torch.int32, device=dev)
+    nnz = D * sum(doc - n + 1 for n in range(1, G + 1))
+    for nO in (4, 32):
+        W = torch.randn(L, nO, device=dev).to(torch.bfloat16)
+        bias = torch.randn(nO, device=dev)
+        dS = torch.randn(D, nO, device=dev)
+        # floors: forward = one table row per entry, the ids, the scores;
+        # backward = the 2 G T keys written and read once (the sort's own
+        # traffic is not counted), dScores once, dWeight written
+        fwd_bytes = 2 * nnz * nO * 2 + D * doc * 8 + D * nO * 4
+        bwd_bytes = 2 * G * D * doc * 8 * 2 + D * nO * 4 + L * nO * 2
+        print(f"sparse_linear (D={D}, T={D * doc}, G={G}, L={L}, bf16, nO={nO}, "
+              f"{2 * nnz} entries):")
+
+        def composed_fwd(w=W):
+            buckets = ops.ngram_buckets(ids, offsets, G, L)
+            return ref.sparse_linear(ids, offsets, w, bias, G, buckets)
+
+        fwd = _alternate({
+            "fused": lambda: hip.sparse_linear_fwd(ids, offsets, W, bias, G),
+            "composed": composed_fwd,
+        })
+        for name, (med, mn) in fwd.items():
+            print(f"  fwd {name:9s} median {med:8.3f} ms  min {mn:8.3f} ms  "
+                  f"{fwd_bytes / med / 1e9:8.3f} TB/s of the {fwd_bytes} floor bytes")
+
+        w = W.clone().requires_grad_(True)
+        Sc = composed_fwd(w)
+
+        def composed_bwd():
+            return torch.autograd.grad(Sc, w, dS, retain_graph=True)[0]
+
+        def fused_bwd():
+            keys = hip.sparse_linear_keys(ids, offsets, G, L)
+            return hip.sparse_linear_bwd(torch.sort(keys).values, dS, L, True)
+
+        keys = hip.sparse_linear_keys(ids, offsets, G, L)
+        diff = (fused_bwd().float() - composed_bwd().float()).abs().max().item()
+        bwd = _alternate({"fused": fused_bwd, "composed": composed_bwd,
+                          "sort": lambda: torch.sort(keys).values})
+        for name, (med, mn) in bwd.items():
+            print(f"  bwd {name:9s} median {med:8.3f} ms  min {mn:8.3f} ms  "
+                  f"{bwd_bytes / med / 1e9:8.3f} TB/s of the {bwd_bytes} floor bytes")
+        print(f"  sort share of the fused backward: "
+              f"{bwd['sort'][0] / bwd['fused'][0]:.2f}")
+        Sf = hip.sparse_linear_fwd(ids, offsets, W, bias, G)
+        print(f"  max |scores fused - composed| = "
+              f"{(Sf - Sc.detach()).abs().max().item():.3e}, "
+              f"max |dW fused - composed| = {diff:.3e}")
+        del Sc, w
+
+
+ALL = {"mwe": bench_mwe, "sparse_linear": bench_sparse_linear, "dpre": bench_dpre, "ce": bench_ce, "mixer": bench_mixer,
        "mwe_dw": bench_mwe_dw,
        "floret": bench_floret, "vecloss": bench_vecloss,
        "most_similar": bench_most_similar, "span_pool": bench_span_pool,
