@@ -1205,30 +1205,24 @@ class _TransitionLoopLoss(torch.autograd.Function):
         dHidden = dS.mm(upperW)
         dSummed = hip.maxout_bwd(dHidden.contiguous(), which, 2).view(-1, HP)
         doc_off, doc_lens, cap_mult, maxlen, doc_total = ctx.doc_layout
-        # Doc-major atomic-free scatter: measured SLOWER than the direct
-        # packed-bf16 atomic kernel on MI355X (12.8-23.6 ms vs 5.3 at 1.9M
-        # rows — the per-(doc,slot) LDS accumulation re-reads dSummed up to
-        # nF times and thrashes L2); kept opt-in for long-doc workloads
-        # where per-destination contention would bite the atomics.
+        # Doc-major arenas (GPU state machines): every (token, slot) row of
+        # dPre has one owning doc, so dpre_gather writes each row once from
+        # an fp32 sum into an UNINITIALIZED buffer — no zero fill, no
+        # atomics.  The host step loop, deterministic mode, oversize docs
+        # and SRX_DPRE=atomic keep the atomic scatter below.
         if (doc_off is not None and not deterministic()
-                and os.environ.get("SRX_DPRE_DOCMAJOR", "0") == "1"
-                and HP % 64 == 0 and 0 < maxlen and maxlen * HP * 4 <= 65536
-                and hasattr(hip, "dpre_scatter_docmajor")):
-            # GPU-state-machine arenas are doc-major: (token, slot) rows are
-            # exclusive to one (doc, slot) stream, so the scatter runs
-            # atomic-free (LDS per-doc accumulation + plain stores) into an
-            # UNINITIALIZED buffer — the direct kernel below is bound by
-            # packed-atomic op rate, not bandwidth.
+                and os.environ.get("SRX_DPRE", "gather") != "atomic"
+                and dSummed.dtype == ctx.pre_dtype
+                and feats.shape[0] == cap_mult * doc_total
+                and HP in (64, 128) and nF <= 16 and maxlen > 0
+                and cap_mult * maxlen <= 256
+                and hip.dpre_gather_slice_bytes(
+                    HP, dSummed.element_size(), cap_mult, maxlen) <= 65536):
             dPre = torch.empty(T1, nF, HP, dtype=ctx.pre_dtype,
                                device=dS.device)
-            # the kernel writes every (token, slot) row of the DOCS; batch
-            # PADDING tokens [doc_total, T1-1) get no contributions — zero
-            # them explicitly (the pad row T1-1 is set from dPad below)
-            if doc_total < T1 - 1:
-                dPre[doc_total:T1 - 1].zero_()
-            dBias32, dPad32 = hip.dpre_scatter_docmajor(
+            dBias32, dPad32 = hip.dpre_gather(
                 dSummed, feats, dPre, doc_off, doc_lens, T1 - 1, cap_mult,
-                maxlen)
+                maxlen, doc_total)
         else:
             # dPre accumulates directly in the compute dtype (bf16: packed
             # atomics, no fp32 buffer + convert); the Zipf-hot pad row and

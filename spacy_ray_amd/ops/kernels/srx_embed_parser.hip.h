@@ -560,82 +560,180 @@ __global__ void parser_step_bwd_kernel(const T* __restrict__ dHidden,
   }
 }
 
-// ------------------------------- batched dPre scatter (doc-major arenas)
-// ATOMIC-FREE variant of dpre_scatter_kernel for the GPU-state-machine
+// ------------------------------- batched dPre gather (doc-major arenas)
+// ATOMIC-FREE replacement of dpre_scatter_kernel for the GPU-state-machine
 // arenas (srx_gpustate.hip), where doc d's transition rows sit at
 // [cap_mult*off[d], cap_mult*(off[d]+len[d])) and every feature of those
-// rows is either the pad row or a token OF DOC d.  (t, f) destinations are
-// therefore exclusive to one (doc, f) stream: one BLOCK per doc
-// accumulates slot f in an LDS fp32 tile [len, HP] (ds-atomic adds across
-// the block's waves) and writes it back with plain coalesced stores —
-// no global atomics.  The direct-atomic kernel measured ~3.7 ms/call at
-// 1.9M rows (packed-bf16 atomic OP RATE bound, ~1.6G pk-atomics); this
-// formulation is plain-store bandwidth bound (~3.3 GB writes).
-// dPre may be UNINITIALIZED (at::empty): every (t<T, f) row is written;
-// the caller still fills the pad row from dPad afterwards.
-// dBias/dPad side sums: register-accumulated, one atomic per column per
-// block (same contract as dpre_scatter_kernel).  fp32 LDS accumulation =
-// single rounding into T — slightly more accurate than packed-bf16
-// atomics; LDS-atomic ordering is not fixed, so SRX_DETERMINISTIC keeps
-// the int64 fixed-point path of the direct kernel.
-template <typename T>
-__global__ __launch_bounds__(256) void dpre_docmajor_kernel(
-    const T* __restrict__ dSummed,      // [cap_total, HP]
-    const int64_t* __restrict__ feats,  // [cap_total, nF]
-    T* __restrict__ dPre,               // [Tb+1, nF, HP]
-    float* __restrict__ dBias,          // [HP]
-    float* __restrict__ dPad,           // [nF, HP]
+// rows is either the pad row or a token OF DOC d.  Each destination row
+// (t, f) therefore has one owner, and the owner writes it ONCE with a plain
+// store from an fp32 sum: no zero fill of dPre, no atomics, no RMW.
+//
+// One wave64 per doc, docs grid-strided over the waves, no block barriers.
+// Lane l owns dword column l of a row (HP bf16 = 64 dwords at HP = 128) and
+// only ever reads back LDS words it wrote itself, so the wave's LDS slice
+// [cap_mult*maxlen rows][LW dwords] needs no synchronisation at all.
+//   Phase A: the doc's dSummed rows go global -> LDS, 16 loads in flight,
+//     adding each lane's columns into the bias accumulators on the way.
+//   Phase B, per slot f: lane r holds the doc-local target of row r
+//     (chunks of 64 rows; the next slot's feats are loaded ahead).  Pad
+//     entries add their rows into pad_acc[f]; for each token t the set bits
+//     of ballot(local == t) name the contributing rows, which are added in
+//     row order in fp32, rounded once (RNE) and stored as one coalesced row.
+//     A destination without contributions is stored as zeros.
+// A feature that is neither pad_row nor inside [off, off+len) is skipped and
+// never indexes LDS or dPre; docs with len <= 0, more rows than the slice,
+// or rows / tokens outside the arrays are skipped whole.
+// Rows wider than 64 dwords (fp32, HP = 128) take NP = 2 column passes.
+// The waves then zero the batch-padding tokens [doc_total, pad_row) and
+// write one fp32 row [HP + nF*HP] of bias | pad sums each, which
+// mwe_colsum_kernel folds in fixed order: the result is bit-reproducible.
+template <typename T, int HP>
+__global__ __launch_bounds__(256) void dpre_gather_kernel(
+    const T* __restrict__ dSummed,      // [S, HP]
+    const int64_t* __restrict__ feats,  // [S, nF]
+    T* __restrict__ dPre,               // [pad_row+1, nF, HP]
+    float* __restrict__ partials,       // [n_waves, HP + nF*HP]
     const int32_t* __restrict__ off, const int32_t* __restrict__ lens,
-    long n_docs, long pad_row, int nF, int HP, int cap_mult) {
-  // 2D grid: block (d, q) owns slot q of doc d — enough independent blocks
-  // (n_docs * nF) that each block's short serial row chain hides under
-  // others (the doc-per-block, q-serial version was latency-bound at
-  // 12.8 ms vs the atomic kernel's 5.3; this shape measures by block
-  // parallelism instead)
-  extern __shared__ float acc[];  // [maxlen][HP]
-  const int tid = threadIdx.x;
-  const int lane = tid & (SRX_WAVE - 1);
-  const int wslot = tid / SRX_WAVE;
+    long n_docs, long S, long pad_row, long doc_total, int nF, int cap_mult,
+    int slice_rows) {
+  constexpr int E = 4 / (int)sizeof(T);  // elements per dword
+  constexpr int D = HP / E;              // dwords per row
+  constexpr int LW = D < SRX_WAVE ? D : SRX_WAVE;
+  constexpr int NP = D / LW;
+  constexpr int MAXF = 16, MAXCH = 4, PF = 16;
+  extern __shared__ uint32_t dg_lds[];
+  const int lane = threadIdx.x & (SRX_WAVE - 1);
+  const int wslot = threadIdx.x / SRX_WAVE;
   const int nw = blockDim.x / SRX_WAVE;
-  const int ncols = HP / SRX_WAVE;  // HP % 64 == 0, HP <= 128
-  const int q = blockIdx.y;
-  float bias_acc[2] = {0.f, 0.f};
-  float pad_acc[2] = {0.f, 0.f};
-  for (long d = blockIdx.x; d < n_docs; d += gridDim.x) {
-    const int n = lens[d];
-    const long o = off[d];
-    const long rbase = (long)cap_mult * o;
-    const int rows = cap_mult * n;
-    for (int i = tid; i < n * HP; i += blockDim.x) acc[i] = 0.f;
-    __syncthreads();
-    for (int r = wslot; r < rows; r += nw) {
-      const long s = rbase + r;
-      const long t = feats[s * (long)nF + q];
-      const T* src = dSummed + s * (long)HP;
-      float x[2];
-      for (int c = 0; c < ncols; c++)
-        x[c] = Elem<T>::ld(src + lane + c * SRX_WAVE);
-      if (q == 0)  // bias = rowsum over ALL rows; q==0 blocks count once
-        for (int c = 0; c < ncols; c++) bias_acc[c] += x[c];
-      if (t == pad_row) {
-        for (int c = 0; c < ncols; c++) pad_acc[c] += x[c];
-      } else {
-        float* a = acc + (size_t)(t - o) * HP;
-        for (int c = 0; c < ncols; c++)
-          atomicAdd(a + lane + c * SRX_WAVE, x[c]);
+  const long wave = (long)blockIdx.x * nw + wslot;
+  const long nwaves = (long)gridDim.x * nw;
+  uint32_t* slice = dg_lds + (size_t)wslot * slice_rows * LW;
+  const uint32_t* src32 = (const uint32_t*)dSummed;
+  uint32_t* dst32 = (uint32_t*)dPre;
+  const bool col_ok = lane < LW;
+  const int lcol = col_ok ? lane : 0;
+  float* prow = partials + wave * (long)(HP + nF * HP);
+
+  auto add_dword = [](uint32_t u, float* a) {
+    if (E == 2) {
+      a[0] += __uint_as_float(u << 16);
+      a[E - 1] += __uint_as_float(u & 0xffff0000u);
+    } else {
+      a[0] += __uint_as_float(u);
+    }
+  };
+  // doc-local target of lane's row in each 64-row chunk for slot f:
+  // >= 0 token, -2 pad, -1 nothing (no row, or a feature outside the doc)
+  auto load_loc = [&](int* loc, long rbase, int rows, long o, int n, int f) {
+#pragma unroll
+    for (int c = 0; c < MAXCH; c++) {
+      const int r = c * SRX_WAVE + lane;
+      loc[c] = -1;
+      if (r < rows) {
+        const int64_t t = feats[(rbase + r) * (long)nF + f];
+        loc[c] = t == pad_row ? -2 : (t >= o && t < o + n) ? (int)(t - o) : -1;
       }
     }
-    __syncthreads();
-    for (int i = tid; i < n * HP; i += blockDim.x) {
-      int local = i / HP, w = i - local * HP;
-      Elem<T>::st(dPre + ((o + local) * (long)nF + q) * HP + w, acc[i]);
+  };
+
+  for (int p = 0; p < NP; p++) {
+    const int j = p * LW + lcol;  // dword column of this lane
+    float bias_acc[E];
+    float pad_acc[MAXF][E];
+#pragma unroll
+    for (int e = 0; e < E; e++) bias_acc[e] = 0.f;
+#pragma unroll
+    for (int k = 0; k < MAXF; k++)
+#pragma unroll
+      for (int e = 0; e < E; e++) pad_acc[k][e] = 0.f;
+
+    for (long d = wave; d < n_docs; d += nwaves) {
+      const int n = lens[d];
+      const long o = off[d];
+      if (n <= 0 || n > slice_rows || o < 0 || o + n > doc_total) continue;
+      const int rows = cap_mult * n;
+      const long rbase = (long)cap_mult * o;
+      if (rows > slice_rows || rbase + rows > S) continue;
+      // ---- phase A: dSummed rows -> LDS, bias sums on the way
+      for (int r0 = 0; r0 < rows; r0 += PF) {
+        uint32_t v[PF];
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+          const int r = r0 + i;
+          v[i] = (r < rows && col_ok) ? src32[(rbase + r) * (long)D + j] : 0u;
+        }
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+          const int r = r0 + i;
+          if (r < rows && col_ok) slice[r * LW + lcol] = v[i];
+          add_dword(v[i], bias_acc);
+        }
+      }
+      // ---- phase B
+      const int nch = (rows + SRX_WAVE - 1) / SRX_WAVE;  // <= MAXCH
+      int loc[MAXCH], nxt[MAXCH] = {-1, -1, -1, -1};
+      load_loc(loc, rbase, rows, o, n, 0);
+      for (int f = 0; f < nF; f++) {
+        if (f + 1 < nF) load_loc(nxt, rbase, rows, o, n, f + 1);
+        float ps[E];
+#pragma unroll
+        for (int e = 0; e < E; e++) ps[e] = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXCH; c++) {
+          if (c < nch) {
+            unsigned long long m = __ballot(loc[c] == -2);
+            while (m) {
+              const int r = c * SRX_WAVE + __builtin_ctzll(m);
+              m &= m - 1;
+              add_dword(slice[r * LW + lcol], ps);
+            }
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < MAXF; k++)
+#pragma unroll
+          for (int e = 0; e < E; e++) pad_acc[k][e] += k == f ? ps[e] : 0.f;
+        for (int t = 0; t < n; t++) {
+          float a[E];
+#pragma unroll
+          for (int e = 0; e < E; e++) a[e] = 0.f;
+#pragma unroll
+          for (int c = 0; c < MAXCH; c++) {
+            if (c < nch) {
+              unsigned long long m = __ballot(loc[c] == t);
+              while (m) {
+                const int r = c * SRX_WAVE + __builtin_ctzll(m);
+                m &= m - 1;
+                add_dword(slice[r * LW + lcol], a);
+              }
+            }
+          }
+          uint32_t u;
+          if (E == 2)
+            u = (uint32_t)f2bf(a[0]) | ((uint32_t)f2bf(a[E - 1]) << 16);
+          else
+            u = __float_as_uint(a[0]);
+          if (col_ok) dst32[((o + t) * (long)nF + f) * D + j] = u;
+        }
+#pragma unroll
+        for (int c = 0; c < MAXCH; c++) loc[c] = nxt[c];
+      }
     }
-    __syncthreads();
-  }
-  for (int c = 0; c < ncols; c++) {
-    if (q == 0 && bias_acc[c] != 0.f)
-      atomicAdd(dBias + lane + c * SRX_WAVE, bias_acc[c]);
-    if (pad_acc[c] != 0.f)
-      atomicAdd(dPad + (long)q * HP + lane + c * SRX_WAVE, pad_acc[c]);
+    // batch-padding tokens own no rows: zero them
+    for (long t = doc_total + wave; t < pad_row; t += nwaves)
+      for (int f = 0; f < nF; f++)
+        if (col_ok) dst32[(t * (long)nF + f) * D + j] = 0u;
+    // this wave's row of bias | pad sums
+    if (col_ok) {
+#pragma unroll
+      for (int e = 0; e < E; e++) prow[E * j + e] = bias_acc[e];
+#pragma unroll
+      for (int k = 0; k < MAXF; k++)
+        if (k < nF)
+#pragma unroll
+          for (int e = 0; e < E; e++)
+            prow[HP + k * HP + E * j + e] = pad_acc[k][e];
+    }
   }
 }
+

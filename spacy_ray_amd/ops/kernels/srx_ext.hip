@@ -650,42 +650,88 @@ std::vector<at::Tensor> dpre_scatter(at::Tensor dSummed, at::Tensor feats,
   return {finish(dBias32), finish(dPad32)};
 }
 
-// Doc-major atomic-free variant (GPU-state-machine arenas): one block per
-// doc, LDS accumulation, plain stores into an UNINITIALIZED dPre — see
-// dpre_docmajor_kernel.  Same return contract as dpre_scatter.
-std::vector<at::Tensor> dpre_scatter_docmajor(at::Tensor dSummed,
-                                              at::Tensor feats, at::Tensor dPre,
-                                              at::Tensor off, at::Tensor lens,
-                                              int64_t pad_row, int64_t cap_mult,
-                                              int64_t maxlen) {
+at::Tensor mwe_fold_partials(at::Tensor part, int ncols, hipStream_t stream);
+
+// LDS bytes of one wave's slice in dpre_gather_kernel: cap_mult*maxlen rows
+// of min(row dwords, 64) dwords.  Python asks this before choosing the path.
+int64_t dpre_gather_slice_bytes(int64_t HP, int64_t elem_size,
+                                int64_t cap_mult, int64_t maxlen) {
+  int64_t row_dwords = HP * elem_size / 4;
+  return cap_mult * maxlen * std::min<int64_t>(row_dwords, SRX_WAVE) * 4;
+}
+
+// Doc-major atomic-free dPre (GPU-state-machine arenas): one wave per doc
+// gathers every (token, slot) row of its doc from LDS and stores it once
+// into an UNINITIALIZED dPre — see dpre_gather_kernel.  Rows [0, pad_row)
+// are all written (batch-padding tokens [doc_total, pad_row) as zeros); the
+// caller fills the pad row from dPad32.  maxlen must be >= max(lens).
+// Same return contract as dpre_scatter.
+std::vector<at::Tensor> dpre_gather(at::Tensor dSummed, at::Tensor feats,
+                                    at::Tensor dPre, at::Tensor off,
+                                    at::Tensor lens, int64_t pad_row,
+                                    int64_t cap_mult, int64_t maxlen,
+                                    int64_t doc_total) {
   check_dev(dSummed);
-  TORCH_CHECK(feats.scalar_type() == at::kLong);
+  check_dev(feats);
+  check_dev(dPre);
+  check_dev(off);
+  check_dev(lens);
+  TORCH_CHECK(feats.scalar_type() == at::kLong && feats.dim() == 2);
+  TORCH_CHECK(off.scalar_type() == at::kInt && lens.scalar_type() == at::kInt &&
+                  off.numel() == lens.numel(),
+              "dpre_gather off/lens must be int32 of one length");
+  TORCH_CHECK(dSummed.is_contiguous() && feats.is_contiguous() &&
+                  dPre.is_contiguous() && off.is_contiguous() &&
+                  lens.is_contiguous(),
+              "dpre_gather needs contiguous tensors");
   TORCH_CHECK(dPre.scalar_type() == dSummed.scalar_type(),
-              "docmajor dPre accumulates in the compute dtype");
+              "dpre_gather writes dPre in the dtype of dSummed");
+  TORCH_CHECK(dSummed.dim() == 2 && dPre.dim() == 3);
+  long S = dSummed.size(0);
   int nF = (int)feats.size(1);
-  int HP = (int)dPre.size(-1);
-  long n_docs = off.size(0);
-  TORCH_CHECK(HP % SRX_WAVE == 0 && HP <= 128, "docmajor needs HP in {64,128}");
-  TORCH_CHECK(nF <= 16, "docmajor nF <= 16");
-  size_t lds = (size_t)maxlen * HP * sizeof(float);
-  TORCH_CHECK(lds <= 64 * 1024, "docmajor maxlen*HP too large for LDS");
-  auto dBias32 = at::zeros({(long)HP}, dSummed.options().dtype(at::kFloat));
-  auto dPad32 =
-      at::zeros({(long)nF, (long)HP}, dSummed.options().dtype(at::kFloat));
-  if (n_docs == 0) return {dBias32, dPad32};
+  int HP = (int)dPre.size(2);
+  long n_docs = off.numel();
+  TORCH_CHECK(HP == 64 || HP == 128, "dpre_gather needs HP in {64, 128}");
+  TORCH_CHECK(nF >= 1 && nF <= 16, "dpre_gather nF <= 16");
+  TORCH_CHECK(feats.size(0) == S && dSummed.size(1) == HP &&
+                  dPre.size(1) == nF,
+              "dpre_gather shape mismatch");
+  TORCH_CHECK(0 <= doc_total && doc_total <= pad_row && pad_row < dPre.size(0),
+              "dpre_gather needs doc_total <= pad_row < dPre rows");
+  TORCH_CHECK(cap_mult >= 1 && maxlen >= 0 && cap_mult * maxlen <= 4 * SRX_WAVE,
+              "dpre_gather holds at most 256 rows per doc");
+  int slice_rows = (int)std::max<int64_t>(cap_mult * maxlen, 1);
+  size_t slice_bytes = (size_t)dpre_gather_slice_bytes(
+      HP, dSummed.element_size(), slice_rows, 1);
+  TORCH_CHECK(slice_bytes <= 64 * 1024, "dpre_gather slice exceeds 64 KB LDS");
+  int nw = (int)std::min<size_t>(4, (64 * 1024) / slice_bytes);
+  // 8 waves per CU cover the LDS-bound occupancy at any slice size
+  long target = std::min<long>(
+      std::max<long>(n_docs, 1),
+      8L * at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
+  int grid = (int)((target + nw - 1) / nw);
+  long n_waves = (long)grid * nw;
+  int ncols = HP + nF * HP;
+  auto partials =
+      at::empty({n_waves, (long)ncols}, dSummed.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentCUDAStream();
-  int grid = (int)std::min<long>(n_docs, 65535);
+#define SRX_DPRE_GATHER(HPV)                                                  \
+  hipLaunchKernelGGL((dpre_gather_kernel<scalar_t, HPV>), dim3(grid),         \
+                     dim3(nw * SRX_WAVE), nw * slice_bytes, stream,           \
+                     (const scalar_t*)dSummed.data_ptr(),                     \
+                     feats.data_ptr<int64_t>(), (scalar_t*)dPre.data_ptr(),   \
+                     partials.data_ptr<float>(), off.data_ptr<int32_t>(),     \
+                     lens.data_ptr<int32_t>(), n_docs, S, (long)pad_row,      \
+                     (long)doc_total, nF, (int)cap_mult, slice_rows)
   DISPATCH_F(dSummed.scalar_type(), {
-    hipLaunchKernelGGL((dpre_docmajor_kernel<scalar_t>),
-                       dim3(grid, (unsigned)nF), dim3(256), lds, stream,
-                       (const scalar_t*)dSummed.data_ptr(),
-                       feats.data_ptr<int64_t>(),
-                       (scalar_t*)dPre.data_ptr(),
-                       dBias32.data_ptr<float>(), dPad32.data_ptr<float>(),
-                       off.data_ptr<int32_t>(), lens.data_ptr<int32_t>(),
-                       n_docs, pad_row, nF, HP, (int)cap_mult);
+    if (HP == 64)
+      SRX_DPRE_GATHER(64);
+    else
+      SRX_DPRE_GATHER(128);
   });
-  return {dBias32, dPad32};
+#undef SRX_DPRE_GATHER
+  auto sums = mwe_fold_partials(partials, ncols, stream);
+  return {sums.slice(0, 0, HP), sums.slice(0, HP).view({(long)nF, (long)HP})};
 }
 
 // ----------------------------------------------------- activations
@@ -2381,7 +2427,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("valid"), py::arg("deterministic") = false);
   m.attr("FIXED_SCALE") = 16777216.0;
   m.def("dpre_scatter", &dpre_scatter);
-  m.def("dpre_scatter_docmajor", &dpre_scatter_docmajor);
+  m.def("dpre_gather", &dpre_gather);
+  m.def("dpre_gather_slice_bytes", &dpre_gather_slice_bytes);
   m.def("run_transition_loop", &srx_run_transition_loop,
         py::call_guard<py::gil_scoped_release>());
   m.def("gpu_arceager", &srx_gpu_arceager, py::arg("pre"), py::arg("off"),

@@ -70,43 +70,65 @@ def bench_mwe():
                                      starts, ends))
 
 
-def bench_dpre():
+def _docmajor_case(nF, cap_mult, n_docs=50000, L=20, HP=128):
+    """Doc-major arenas as the GPU state machines lay them out: doc d owns
+    rows [cap_mult*d*L, cap_mult*(d+1)*L), each feature a token of doc d or
+    (a quarter of them) the pad row; dSummed with the maxout zero pattern."""
     import numpy as np
 
-    nF, HP, L = 13, 128, 20
-    n_docs = 50000
     T = n_docs * L
-    SS = 2 * T
+    SS = cap_mult * T
     rng = np.random.default_rng(0)
-    # doc-major feats: row r of doc d draws from doc d's tokens or pad
-    doc = np.repeat(np.arange(n_docs, dtype=np.int64), 2 * L)
-    base = doc * L
-    f = base[:, None] + rng.integers(0, L, (SS, nF))
-    pad = rng.random((SS, nF)) < 0.25
-    f[pad] = T
+    doc = np.repeat(np.arange(n_docs, dtype=np.int64), cap_mult * L)
+    f = (doc * L)[:, None] + rng.integers(0, L, (SS, nF))
+    f[rng.random((SS, nF)) < 0.25] = T
     feats = torch.from_numpy(f).to(dev)
     dS = torch.randn(SS, HP, device=dev, dtype=torch.bfloat16)
-    # realistic sparsity: dSummed comes out of maxout_bwd — exactly one of
-    # each piece pair (h, H+h) is nonzero
     pick = torch.randint(0, 2, (SS, 1, HP // 2), device=dev)
     dS.view(SS, 2, HP // 2).scatter_(1, pick, 0.0)
-    dPre = torch.zeros(T + 1, nF, HP, device=dev, dtype=torch.bfloat16)
-    timeit("dpre_scatter bf16 (1.9M rows)",
-           lambda: hip.dpre_scatter(dS, feats, dPre, T))
     off = torch.arange(n_docs, device=dev, dtype=torch.int32) * L
     lens = torch.full((n_docs,), L, device=dev, dtype=torch.int32)
-    dPre2 = torch.empty(T + 1, nF, HP, device=dev, dtype=torch.bfloat16)
-    timeit("dpre_docmajor bf16 (1.9M rows)",
-           lambda: hip.dpre_scatter_docmajor(dS, feats, dPre2, off, lens,
-                                             T, 2, L))
-    # diagnostics: atomic-op-rate hypothesis — nF=1 should be ~1/13 the
-    # time if op-bound; fp32 (2x the ops of packed bf16) should be ~2x
+    return T, dS, feats, off, lens
+
+
+def bench_dpre():
+    """torch.zeros + dpre_scatter (packed-bf16 atomics) against torch.empty +
+    dpre_gather (one wave per doc, plain stores) on the same doc-major
+    inputs, at the parser shape (nF = 13, cap_mult = 2) and the NER shape
+    (nF = 6, cap_mult = 1): 1M tokens in 20-word docs, HP = 128, bf16.  The
+    two alternate in one loop; median (min) of 30 event-timed calls after 10
+    warm-ups.  Floor bytes of the gather: dSummed and feats read once, dPre
+    written once."""
+    L, HP = 20, 128
+    for label, nF, cap_mult in (("parser", 13, 2), ("NER", 6, 1)):
+        T, dS, feats, off, lens = _docmajor_case(nF, cap_mult, L=L, HP=HP)
+        SS = feats.shape[0]
+
+        def atomic():
+            dPre = torch.zeros(T + 1, nF, HP, device=dev, dtype=torch.bfloat16)
+            return hip.dpre_scatter(dS, feats, dPre, T)
+
+        def gather():
+            dPre = torch.empty(T + 1, nF, HP, device=dev, dtype=torch.bfloat16)
+            return hip.dpre_gather(dS, feats, dPre, off, lens, T, cap_mult, L, T)
+
+        floor = SS * HP * 2 + SS * nF * 8 + T * nF * HP * 2
+        res = _alternate({"zeros + dpre_scatter": atomic,
+                          "empty + dpre_gather": gather})
+        print(f"dpre {label} (T={T}, rows={SS}, nF={nF}, HP={HP}, bf16):")
+        for name, (med, mn) in res.items():
+            print(f"  {name:22s} median {med:8.3f} ms  min {mn:8.3f} ms  "
+                  f"{floor / med / 1e9:6.3f} TB/s of the {floor / 1e9:.2f} GB "
+                  f"gather floor")
+    # diagnostics of the atomic kernel: nF=1 should be ~1/13 the time if
+    # op-bound; fp32 (2x the ops of packed bf16) should be ~2x
+    T, dS, feats, off, lens = _docmajor_case(13, 2, L=L, HP=HP)
     feats1 = feats[:, :1].contiguous()
     dPre1 = torch.zeros(T + 1, 1, HP, device=dev, dtype=torch.bfloat16)
     timeit("dpre_scatter bf16 nF=1",
            lambda: hip.dpre_scatter(dS, feats1, dPre1, T))
     dS32 = dS.float()
-    dPre32 = torch.zeros(T + 1, nF, HP, device=dev, dtype=torch.float32)
+    dPre32 = torch.zeros(T + 1, 13, HP, device=dev, dtype=torch.float32)
     timeit("dpre_scatter fp32 (2x ops)",
            lambda: hip.dpre_scatter(dS32, feats, dPre32, T))
 
