@@ -99,7 +99,10 @@ def component_to_thinc_nodes(pipe) -> List[Tuple[str, Dict[str, np.ndarray]]]:
         enc = mod if t2v is None else t2v
         embed = enc.embed
         nodes.append(("tok2vec", {}))
-        nodes.append(("multihashembed", {}))
+        if hasattr(embed, "E"):  # CharacterEmbed: byte table, then the hashed one
+            nodes.append(("charembed", {"E": npf(embed.E)}))
+        else:
+            nodes.append(("multihashembed", {}))
         for i, table in enumerate(embed.tables):
             nodes.append((f"hashembed>>{embed.attrs[i]}", {"E": npf(table)}))
         if getattr(embed, "static_vectors", None) is not None:
@@ -146,6 +149,8 @@ def load_thinc_nodes_into_component(pipe, data: bytes) -> int:
         out = []
         if enc is not None:
             embed = enc.embed
+            if hasattr(embed, "E"):
+                out.append(("charembed", "E", embed.E))
             for i, table in enumerate(embed.tables):
                 out.append((f"hashembed>>{embed.attrs[i]}", "E", table))
             if getattr(embed, "static_vectors", None) is not None:

@@ -11,7 +11,7 @@ import contextlib
 from typing import List, Optional
 
 from spacy_ray_amd.config.registry import registry
-from .tok2vec import MaxoutWindowEncoder, MultiHashEmbed, Tok2Vec
+from .tok2vec import CharacterEmbed, MaxoutWindowEncoder, MultiHashEmbed, Tok2Vec
 from .parser_model import TransitionModel
 
 
@@ -42,6 +42,30 @@ def make_multi_hash_embed(
             vocab=_vocab_for_build() if include_static_vectors else None)
 
     return ModelSpec(build, width=width, kind="embed")
+
+
+@registry.architectures("spacy.CharacterEmbed.v2")
+def make_character_embed(
+    width: int,
+    rows: int,
+    nM: int,
+    nC: int,
+    include_static_vectors: bool = False,
+    feature: str = "NORM",
+):
+    if include_static_vectors:
+        raise ValueError(
+            "spacy.CharacterEmbed.v2: include_static_vectors = true is not "
+            "supported yet; use spacy.MultiHashEmbed.v2 for static vectors")
+    from spacy_ray_amd.vocab.attrs import ATTR_NAMES
+
+    if feature not in ATTR_NAMES:
+        raise ValueError(
+            f"spacy.CharacterEmbed.v2: feature must be one of "
+            f"{list(ATTR_NAMES)}, got {feature!r}")
+    return ModelSpec(
+        lambda: CharacterEmbed(width, rows=rows, nM=nM, nC=nC, feature=feature),
+        width=width, kind="embed")
 
 
 # Modules are built inside pipe.initialize / pipe.load_cfg, which know no

@@ -100,6 +100,22 @@ class TokenBatch:
             self.staged[key] = self._build_vec_rows(key_attr)
         return self.staged[key]
 
+    def get_char_ids(self, nC: int) -> torch.Tensor:
+        """uint8 [T, nC] device tensor of Doc.to_utf8_array(nC) per doc (pad
+        pseudo-doc rows all 255), built on first use and kept in `staged`."""
+        key = ("char_ids", nC)
+        if key not in self.staged:
+            from spacy_ray_amd.utils.pinned import to_device
+
+            parts = [d.to_utf8_array(nC) for d in self.docs]
+            n_pad = self.n_tokens - self.n_real_tokens
+            if n_pad > 0:
+                parts.append(np.full((n_pad, nC), 255, dtype=np.uint8))
+            ids = (np.concatenate(parts, axis=0) if parts
+                   else np.zeros((0, nC), dtype=np.uint8))
+            self.staged[key] = to_device(ids, self.attr_ids.device)
+        return self.staged[key]
+
     # -------------------------------------------------------------- floret
     def _build_floret(self, key_attr: str):
         """Host side of the floret path: deduplicate the tokens over their

@@ -1,4 +1,4 @@
-"""CNN tok2vec: MultiHashEmbed + MaxoutWindowEncoder.
+"""CNN tok2vec: MultiHashEmbed or CharacterEmbed + MaxoutWindowEncoder.
 
 Behavioral contract of spaCy's default tok2vec: 4 attrs
 (NORM/PREFIX/SUFFIX/SHAPE) each hash-embedded (4 murmur rows summed), the
@@ -7,14 +7,46 @@ seq2col(window=1) -> Maxout -> LayerNorm.
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, Optional, Union
 
 import torch
 import torch.nn as nn
 
 from spacy_ray_amd.ops import api as ops
+from spacy_ray_amd.vocab.attrs import ATTR_NAMES
 from .batch import TokenBatch
 from .layers import LayerNorm, Maxout, StaticVectors
+
+
+def _mix(mixer: Maxout, X: torch.Tensor, drop: float, training: bool) -> torch.Tensor:
+    """The embed mixer (Maxout + LayerNorm + dropout) of MultiHashEmbed and
+    CharacterEmbed over the concatenated blocks X."""
+    from spacy_ray_amd.utils import timing
+
+    if ops.mixer_layer_available(X, mixer.nO, mixer.pieces):
+        # GEMM + maxout + LayerNorm in ONE MFMA kernel.  The kernels take
+        # a dropout mask too, but a mask from ops.dropout_mask_like drops
+        # other elements than F.dropout and moved the benchmark's
+        # parameter norms by more than the documented 2^-8 run-to-run
+        # noise (docs/KERNELS.md), so dropout stays torch's, after.
+        with timing.phase("t2v/mixer_fused"):
+            Y = ops.mixer_layer(X, mixer.weight, mixer.bias,
+                                mixer.norm.weight, mixer.norm.bias,
+                                None, mixer.norm.eps)
+        with timing.phase("t2v/mixer_drop"):
+            if drop and training:
+                Y = torch.nn.functional.dropout(Y, drop)
+        return Y
+    with timing.phase("t2v/mixer_gemm"):
+        Y = ops.linear_cdw(X, mixer.weight, mixer.bias)
+    with timing.phase("t2v/mixer_maxout"):
+        Y = ops.maxout(Y.view(*Y.shape[:-1], mixer.pieces, mixer.nO))
+    with timing.phase("t2v/mixer_ln"):
+        Y = mixer.norm(Y)
+    with timing.phase("t2v/mixer_drop"):
+        if drop and training:
+            Y = torch.nn.functional.dropout(Y, drop)
+    return Y
 
 
 class MultiHashEmbed(nn.Module):
@@ -67,31 +99,44 @@ class MultiHashEmbed(nn.Module):
                 vectors = (*sv.table_and_rows(batch), sv.W)
             X = ops.multi_hashembed(batch.attr_ids, self.seeds,
                                     list(self.tables), vectors)
-        mixer = self.mixer
-        if ops.mixer_layer_available(X, mixer.nO, mixer.pieces):
-            # GEMM + maxout + LayerNorm in ONE MFMA kernel.  The kernels take
-            # a dropout mask too, but a mask from ops.dropout_mask_like drops
-            # other elements than F.dropout and moved the benchmark's
-            # parameter norms by more than the documented 2^-8 run-to-run
-            # noise (docs/KERNELS.md), so dropout stays torch's, after.
-            with timing.phase("t2v/mixer_fused"):
-                Y = ops.mixer_layer(X, mixer.weight, mixer.bias,
-                                    mixer.norm.weight, mixer.norm.bias,
-                                    None, mixer.norm.eps)
-            with timing.phase("t2v/mixer_drop"):
-                if drop and self.training:
-                    Y = torch.nn.functional.dropout(Y, drop)
-            return Y
-        with timing.phase("t2v/mixer_gemm"):
-            Y = ops.linear_cdw(X, self.mixer.weight, self.mixer.bias)
-        with timing.phase("t2v/mixer_maxout"):
-            Y = ops.maxout(Y.view(*Y.shape[:-1], self.mixer.pieces, self.mixer.nO))
-        with timing.phase("t2v/mixer_ln"):
-            Y = self.mixer.norm(Y)
-        with timing.phase("t2v/mixer_drop"):
-            if drop and self.training:
-                Y = torch.nn.functional.dropout(Y, drop)
-        return Y
+        return _mix(self.mixer, X, drop, self.training)
+
+
+class CharacterEmbed(nn.Module):
+    """spacy.CharacterEmbed.v2: a per-position byte table E [nC, 256, nM]
+    over each token's first and last UTF-8 bytes (Doc.to_utf8_array) beside
+    ONE hashed `feature` table, mixed down to `width` by Maxout + LayerNorm.
+    `tables` / `attrs` / `mixer` follow MultiHashEmbed's names."""
+
+    def __init__(self, width: int, rows: int, nM: int, nC: int,
+                 feature: str = "NORM", seed: int = 5):
+        super().__init__()
+        if feature not in ATTR_NAMES:
+            raise ValueError(
+                f"spacy.CharacterEmbed.v2: feature must be one of "
+                f"{list(ATTR_NAMES)}, got {feature!r}")
+        if nM < 1 or nC < 1 or rows < 1:
+            raise ValueError("spacy.CharacterEmbed.v2: rows, nM and nC must be >= 1")
+        self.width = width
+        self.nM = nM
+        self.nC = nC
+        self.attrs = [feature]
+        self.column = ATTR_NAMES.index(feature)
+        self.seeds = [seed]
+        self.E = nn.Parameter(torch.empty(nC, 256, nM).uniform_(-0.1, 0.1))
+        self.tables = nn.ParameterList(
+            [nn.Parameter(torch.randn(rows, width) * (1.0 / (width ** 0.5)))])
+        self.mixer = Maxout(nC * nM + width, width, pieces=3, normalize=True)
+        self.static_vectors = None
+
+    def forward(self, batch: TokenBatch, drop: float = 0.0) -> torch.Tensor:
+        from spacy_ray_amd.utils import timing
+
+        with timing.phase("t2v/embed_tables"):
+            X = ops.char_embed(self.E, batch.get_char_ids(self.nC),
+                               self.tables[0], batch.attr_ids[:, self.column],
+                               self.seeds[0])
+        return _mix(self.mixer, X, drop, self.training)
 
 
 class MaxoutWindowEncoder(nn.Module):
@@ -135,7 +180,8 @@ class MaxoutWindowEncoder(nn.Module):
 class Tok2Vec(nn.Module):
     """embed -> encode; output width = encode.width."""
 
-    def __init__(self, embed: MultiHashEmbed, encode: MaxoutWindowEncoder):
+    def __init__(self, embed: Union[MultiHashEmbed, CharacterEmbed],
+                 encode: MaxoutWindowEncoder):
         super().__init__()
         self.embed = embed
         self.encode = encode

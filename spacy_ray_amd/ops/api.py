@@ -449,6 +449,135 @@ def multi_hashembed_vectors(ids4: torch.Tensor, seeds, tables,
                       static_vectors(vW, vtable, vrows)], dim=1)
 
 
+# ------------------------------------------------------- character embed
+# spacy.CharacterEmbed.v2's embedding: a per-position byte table E [nC, 256,
+# nM] next to ONE hashed table, the two blocks side by side in [T, nC nM + W].
+# Fused kernels (srx_charembed.hip.h: a 16-byte gather, an LDS histogram)
+# against the composed path (advanced indexing, index_add_, hashembed + cat).
+# A direction is on by default only where tools/kbench.py char_embed measured
+# it not slower (profiles/README.md); SRX_CHAR_EMBED=fused / composed
+# overrides both directions.  Measured (T = 1M, nC = 8, nM = 64, bf16):
+# forward 0.35 ms against 1.99 ms, backward 2.68 ms against 9.86 ms.
+CHAR_EMBED_FUSED_DEFAULT = {"fwd": True, "bwd": True}
+
+
+def _char_embed_mode() -> str:
+    mode = os.environ.get("SRX_CHAR_EMBED", "")
+    if mode not in ("", "fused", "composed"):
+        raise ValueError(
+            f"SRX_CHAR_EMBED={mode!r}: expected 'fused' or 'composed'")
+    return mode
+
+
+def char_embed_available(E: torch.Tensor, ids: torch.Tensor,
+                         hash_table: torch.Tensor) -> bool:
+    """The fused kernels' fast path: bf16 or fp32 tables of one dtype on the
+    GPU, nM % 8 == 0 in 8..128, nC in 1..16, uint8 ids [T, nC]."""
+    if not (E.is_cuda and E.dim() == 3 and ids.dim() == 2):
+        return False
+    nC, bins, nM = E.shape
+    vec = 8 if E.dtype == torch.bfloat16 else 4
+    return (
+        E.dtype in (torch.bfloat16, torch.float32)
+        and hash_table.is_cuda
+        and hash_table.dtype == E.dtype
+        and hash_table.dim() == 2
+        and hash_table.is_contiguous()
+        and bins == 256
+        and 1 <= nC <= 16
+        and nM % 8 == 0
+        and 8 <= nM <= 128
+        and E.is_contiguous()
+        and ids.is_cuda
+        and ids.dtype == torch.uint8
+        and ids.shape[1] == nC
+        and ids.is_contiguous()
+        and (nC * nM + hash_table.shape[1]) % vec == 0
+        and ids.shape[0] * nC * (nM // vec) < 2 ** 31
+        and hip_ext() is not None
+    )
+
+
+class _CharTable(torch.autograd.Function):
+    """The composed byte-table block: E[c, ids[t, c]] by advanced indexing,
+    index_add_ backward (also the CPU path)."""
+
+    @staticmethod
+    def forward(ctx, E, ids):
+        ctx.save_for_backward(ids)
+        ctx.shape = tuple(E.shape)
+        return ref.char_embed_forward(E, ids)
+
+    @staticmethod
+    def backward(ctx, dX):
+        (ids,) = ctx.saved_tensors
+        nC, _, nM = ctx.shape
+        return ref.char_embed_backward(dX, ids, nC, nM), None
+
+
+class _CharEmbed(torch.autograd.Function):
+    """[T, nC nM + W] in one node: char_embed_fwd writes the byte block, the
+    hashembed forward writes its block of the same buffer (no torch.cat);
+    the backward reads both column blocks of dX in place."""
+
+    @staticmethod
+    def forward(ctx, E, ids, hash_table, hash_ids, seed, fused_fwd, fused_bwd):
+        hip = hip_ext()
+        nC, _, nM = E.shape
+        W = hash_table.shape[1]
+        off = nC * nM
+        X = E.new_empty(ids.shape[0], off + W)
+        if fused_fwd:
+            hip.char_embed_fwd(E, ids, X, 0)
+        else:
+            X[:, :off] = ref.char_embed_forward(E, ids)
+        ids1 = hash_ids.unsqueeze(1)
+        key = None
+        if _multi_fwd_ok(ids1, [hash_table]):
+            rows, key = (t[0] for t in hip.multi_hashembed_fwd(
+                ids1, [hash_table], [int(seed)], X, off))
+        else:
+            _, rows = hip.hashembed_fwd(hash_table, hash_ids.contiguous(),
+                                        int(seed), X, off)
+        ctx.save_for_backward(ids, rows, *([] if key is None else [key]))
+        ctx.dims = (nC, nM, hash_table.shape[0])
+        ctx.fused_bwd = fused_bwd
+        return X
+
+    @staticmethod
+    def backward(ctx, dX):
+        ids, rows, *key = ctx.saved_tensors
+        nC, nM, nrows = ctx.dims
+        off = nC * nM
+        if dX.stride(1) != 1:
+            dX = dX.contiguous()
+        if ctx.fused_bwd:
+            dE = hip_ext().char_embed_bwd(dX[:, :off], ids, nC, nM,
+                                          deterministic())
+        else:
+            dE = ref.char_embed_backward(dX[:, :off], ids, nC, nM)
+        dT = _hashembed_table_grad(dX[:, off:], rows, key[0] if key else None,
+                                   nrows)
+        return dE, None, dT, None, None, None, None
+
+
+def char_embed(E: torch.Tensor, ids: torch.Tensor, hash_table: torch.Tensor,
+               hash_ids: torch.Tensor, seed: int) -> torch.Tensor:
+    """E [nC, 256, nM], ids uint8 [T, nC], one HashEmbed table [R, W] over
+    hash_ids int64 [T] -> X [T, nC nM + W], the byte block first."""
+    mode = _char_embed_mode()  # a bad SRX_CHAR_EMBED raises on every path
+    if E.is_cuda and mode != "composed":
+        _want_hip(E)  # a GPU run without the extension is an error
+        if char_embed_available(E, ids, hash_table):
+            fwd = mode == "fused" or CHAR_EMBED_FUSED_DEFAULT["fwd"]
+            bwd = mode == "fused" or CHAR_EMBED_FUSED_DEFAULT["bwd"]
+            if fwd or bwd:
+                return _CharEmbed.apply(E, ids, hash_table, hash_ids, seed,
+                                        fwd, bwd)
+    return torch.cat([_CharTable.apply(E, ids),
+                      hashembed(hash_table, hash_ids.contiguous(), seed)], dim=1)
+
+
 # -------------------------------------------------------- floret vectors
 # floret_words_mean kernel (srx_floret.hip.h) against the composed path
 # (index_select + segment sum + divide): the same rule and the same switch as

@@ -22,6 +22,7 @@
 #include "srx_vecloss.hip.h"
 #include "srx_spanpool.hip.h"
 #include "srx_sparselinear.hip.h"
+#include "srx_charembed.hip.h"
 #include "srx_activations.hip.h"
 #include "srx_attn.hip.h"
 
@@ -2239,6 +2240,119 @@ at::Tensor sparse_linear_bwd(at::Tensor sorted, at::Tensor dS, long L, bool as_b
   return dW;
 }
 
+// ------------------------------------------------- CharacterEmbed
+// see srx_charembed.hip.h.  E bf16 / fp32 [nC, 256, nM], ids uint8 [T, nC];
+// nM % 8 == 0, 8 <= nM <= 128, 1 <= nC <= 16, 16-byte-aligned blocks.
+namespace ce {
+
+constexpr long kMinTokensPerSlice = 4096;
+
+inline void check_shape(long nC, long nM) {
+  TORCH_CHECK(nC >= 1 && nC <= 16, "char_embed: nC must be in 1..16");
+  TORCH_CHECK(nM >= 8 && nM <= 128 && nM % 8 == 0,
+              "char_embed: nM must be a multiple of 8 in 8..128");
+}
+
+inline void check_ids(const at::Tensor& ids, long nC) {
+  check_dev(ids);
+  TORCH_CHECK(ids.scalar_type() == at::kByte && ids.dim() == 2 && ids.size(1) == nC,
+              "char_embed: ids must be uint8 [T, nC]");
+}
+
+}  // namespace ce
+
+// -> (S, tokens per slice) of char_embed_bwd's grid (nC, S): nC * S is about
+// twice the CU count, but a slice never holds fewer than kMinTokensPerSlice
+// tokens (each slice costs a zero fill, a write and a read of [256, nM]
+// floats), so small batches run S = 1.
+std::vector<int64_t> char_embed_slices(int64_t T, int64_t nC) {
+  ce::check_shape(nC, 8);
+  const long cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  long S = std::max<long>(1, (2 * cus + nC / 2) / nC);
+  S = std::max<long>(1, std::min<long>(S, T / ce::kMinTokensPerSlice));
+  const long per = std::max<long>(1, (T + S - 1) / S);
+  S = std::max<long>(1, (T + per - 1) / per);  // no empty slice
+  return {S, per};
+}
+
+void char_embed_fwd(at::Tensor E, at::Tensor ids, at::Tensor X, int64_t col_off) {
+  check_dev(E);
+  TORCH_CHECK(E.dim() == 3 && E.size(1) == SRX_CE_BINS,
+              "char_embed_fwd: E must be [nC, 256, nM]");
+  const long nC = E.size(0), nM = E.size(2);
+  ce::check_shape(nC, nM);
+  ce::check_ids(ids, nC);
+  const long nT = ids.size(0);
+  TORCH_CHECK(X.is_cuda() && X.dim() == 2 && X.is_contiguous() && X.size(0) == nT &&
+                  X.scalar_type() == E.scalar_type(),
+              "X must be a contiguous GPU [T, ldX] matrix of the table's dtype");
+  const long ldX = X.size(1);
+  TORCH_CHECK(col_off >= 0 && col_off + nC * nM <= ldX,
+              "char_embed_fwd: column block outside X");
+  if (nT == 0) return;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  DISPATCH_F(E.scalar_type(), {
+    const long items = nT * nC * (nM / kVec);
+    TORCH_CHECK(items < 2147483648L, "char_embed_fwd: T * nC * nM too large");
+    TORCH_CHECK(ldX % kVec == 0 && col_off % kVec == 0 && aligned16(X.data_ptr()) &&
+                    aligned16(E.data_ptr()),
+                "char_embed_fwd: blocks not 16-byte aligned");
+    hipLaunchKernelGGL((char_embed_fwd_kernel<scalar_t, kVec>),
+                       dim3((unsigned)((items + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       stream, (const scalar_t*)E.data_ptr(), ids.data_ptr<uint8_t>(),
+                       (scalar_t*)X.data_ptr() + col_off, nT, (int)nC, (int)nM, ldX);
+  });
+}
+
+// dE [nC, 256, nM] in dX's dtype; dX is the [T, nC * nM] column block of the
+// embed gradient (a row view, innermost stride 1, read in place).
+at::Tensor char_embed_bwd(at::Tensor dX, at::Tensor ids, int64_t nC, int64_t nM,
+                          bool deterministic) {
+  ce::check_shape(nC, nM);
+  ce::check_ids(ids, nC);
+  const long nT = ids.size(0);
+  TORCH_CHECK(dX.is_cuda() && dX.dim() == 2 && dX.stride(1) == 1 && dX.size(0) == nT &&
+                  dX.size(1) == nC * nM,
+              "char_embed_bwd: dX must be a GPU [T, nC * nM] row view");
+  const long ldX = nT > 1 ? dX.stride(0) : nC * nM;
+  auto dE = at::empty({nC, (long)SRX_CE_BINS, nM}, dX.options());
+  if (nT == 0) return dE.zero_();
+  const auto sl = char_embed_slices(nT, nC);
+  const long S = sl[0], per = sl[1];
+  const long n = nC * SRX_CE_BINS * nM;
+  auto part = at::empty({S, n}, dX.options().dtype(at::kFloat));
+  const size_t lds = (size_t)SRX_CE_BINS * nM * sizeof(float);
+  const dim3 grid((unsigned)nC, (unsigned)S);
+  auto stream = at::cuda::getCurrentCUDAStream();
+#define SRX_CE_BWD(DET_, NT_)                                                       \
+  {                                                                                 \
+    static bool attr_set = false;                                                   \
+    if (!attr_set) {                                                                \
+      (void)hipFuncSetAttribute(                                                    \
+          (const void*)char_embed_bwd_kernel<scalar_t, kVec, DET_>,                 \
+          hipFuncAttributeMaxDynamicSharedMemorySize, SRX_CE_BINS * 128 * 4);       \
+      attr_set = true;                                                              \
+    }                                                                               \
+    hipLaunchKernelGGL((char_embed_bwd_kernel<scalar_t, kVec, DET_>), grid,         \
+                       dim3(NT_), lds, stream, (const scalar_t*)dX.data_ptr(),      \
+                       ids.data_ptr<uint8_t>(), part.data_ptr<float>(), nT, per,    \
+                       (int)nC, (int)nM, ldX);                                      \
+  }
+  DISPATCH_F(dX.scalar_type(), {
+    TORCH_CHECK(ldX % kVec == 0 && aligned16(dX.data_ptr()),
+                "char_embed_bwd: dX rows not 16-byte aligned");
+    if (deterministic)
+      SRX_CE_BWD(true, SRX_WAVE)
+    else
+      SRX_CE_BWD(false, SRX_CE_THREADS)
+    hipLaunchKernelGGL((char_embed_reduce_kernel<scalar_t, kVec>),
+                       dim3((unsigned)((n / kVec + kBlock - 1) / kBlock)), dim3(kBlock),
+                       0, stream, part.data_ptr<float>(), (scalar_t*)dE.data_ptr(), n, S);
+  });
+#undef SRX_CE_BWD
+  return dE;
+}
+
 // --------------------------------------------- fused transition step (C++)
 // One python call per transition step: state scorer kernel + upper GEMM +
 // on-device action selection, with a C++ autograd node so the per-step
@@ -2421,6 +2535,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sparse_linear_bwd", &sparse_linear_bwd, py::arg("sorted"),
         py::arg("dScores"), py::arg("length"), py::arg("as_bf16"),
         py::arg("max_blocks") = 0);
+  m.def("char_embed_slices", &char_embed_slices, py::arg("T"), py::arg("nC"));
+  m.def("char_embed_fwd", &char_embed_fwd, py::arg("E"), py::arg("ids"), py::arg("X"),
+        py::arg("col_off") = 0);
+  m.def("char_embed_bwd", &char_embed_bwd, py::arg("dX_view"), py::arg("ids"),
+        py::arg("nC"), py::arg("nM"), py::arg("deterministic") = false);
   m.def("fused_step",&fusedstep::fused_step);
   m.def("fused_entries_take", &fusedstep::fused_entries_take);
   m.def("transition_ce", &transition_ce, py::arg("scores"), py::arg("gold"),

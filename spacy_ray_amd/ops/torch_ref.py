@@ -89,6 +89,26 @@ def hashembed_backward(dY: torch.Tensor, rows: torch.Tensor, nrows: int) -> torc
     return dT
 
 
+def char_embed_forward(E: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """E [nC, 256, nM], ids uint8 [T, nC] -> [T, nC * nM]: position c of
+    token t embeds as E[c, ids[t, c]] (Thinc CharacterEmbed contract)."""
+    nC = E.shape[0]
+    pos = torch.arange(nC, device=ids.device)
+    return E[pos, ids.long()].reshape(ids.shape[0], -1)
+
+
+def char_embed_backward(dX: torch.Tensor, ids: torch.Tensor, nC: int,
+                        nM: int) -> torch.Tensor:
+    """dE [nC, 256, nM]: every occurrence of a byte adds its gradient row
+    (the true sum; see docs/PARITY.md).  16-bit gradients are summed in
+    fp32: a hot bin takes most of the batch's tokens."""
+    flat = (ids.long() + 256 * torch.arange(nC, device=ids.device)).reshape(-1)
+    acc = torch.float32 if dX.element_size() < 4 else dX.dtype
+    dE = torch.zeros(nC * 256, nM, dtype=acc, device=dX.device)
+    dE.index_add_(0, flat, dX.reshape(-1, nM).to(acc))
+    return dE.to(dX.dtype).view(nC, 256, nM)
+
+
 def static_vectors_gather(table: torch.Tensor, rows: torch.Tensor, nM: int) -> torch.Tensor:
     """table[rows][:, :nM] with out-of-vocabulary rows (rows < 0) ZEROED
     AFTER the gather (the index is only made valid, never trusted)."""

@@ -93,6 +93,7 @@ class Doc:
         "vocab", "words", "spaces", "attr_hashes",
         "tags", "heads", "deps", "ents", "sent_starts", "cats", "morphs",
         "lemmas", "spans", "tensor", "user_data", "vector_rows",
+        "utf8_arrays",
     )
 
     def __init__(
@@ -137,9 +138,39 @@ class Doc:
         # key_attr -> (Vectors, int32 rows [n]); filled lazily by
         # get_vector_rows and shared with copy_unannotated, like attr_hashes
         self.vector_rows: Dict[str, tuple] = {}
+        # nr_char -> uint8 [n, nr_char]; filled by to_utf8_array, shared
+        # with copy_unannotated
+        self.utf8_arrays: Dict[int, np.ndarray] = {}
 
     def __len__(self) -> int:
         return len(self.words)
+
+    def to_utf8_array(self, nr_char: int = -1) -> np.ndarray:
+        """uint8 [len(doc), nr_char]: the UTF-8 bytes of each token's text in
+        the order first, last, second, second-to-last, ...; no byte is used
+        twice, unused columns hold 255 (spaCy's Doc.to_utf8_array).
+        nr_char = -1 takes the longest token's byte count."""
+        enc = [w.encode("utf8") for w in self.words]
+        if nr_char == -1:
+            nr_char = max((len(b) for b in enc), default=0)
+        if nr_char < 0:
+            raise ValueError(f"to_utf8_array: nr_char must be >= 0, got {nr_char}")
+        cached = self.utf8_arrays.get(nr_char)
+        if cached is not None:
+            return cached
+        n_head, n_tail = (nr_char + 1) // 2, nr_char // 2
+        out = np.full((len(enc), nr_char), 255, dtype=np.uint8)
+        for i, b in enumerate(enc):
+            # columns 0, 2, 4, ... walk in from the front, 1, 3, 5, ... from
+            # the back; together they take min(len, nr_char) distinct bytes
+            k = min(len(b), nr_char)
+            h, t = min(n_head, (k + 1) // 2), min(n_tail, k // 2)
+            if h:
+                out[i, 0:2 * h:2] = np.frombuffer(b[:h], dtype=np.uint8)
+            if t:
+                out[i, 1:2 * t:2] = np.frombuffer(b[:-t - 1:-1], dtype=np.uint8)
+        self.utf8_arrays[nr_char] = out
+        return out
 
     def get_vector_rows(self, key_attr: Optional[str] = None) -> np.ndarray:
         """Rows of this doc's tokens in vocab.vectors (-1 = OOV).  "ORTH"
@@ -235,6 +266,7 @@ class Doc:
         doc = Doc(self.vocab, self.words, spaces=self.spaces,
                   attr_hashes=self.attr_hashes)
         doc.vector_rows = self.vector_rows
+        doc.utf8_arrays = self.utf8_arrays
         return doc
 
     def to_dict(self) -> Dict:

@@ -916,13 +916,82 @@ def bench_sparse_linear():
         del Sc, w
 
 
+def bench_char_embed():
+    """char_embed_fwd / char_embed_bwd (srx_charembed.hip.h) against the
+    composed path (advanced indexing, index_add_) on the same inputs: T =
+    1,048,576 tokens, nC = 8, nM = 64, bf16; ids letter-heavy (Zipf over 26
+    letters, a few other bytes) with about a third of the cells 255.  Both
+    sides write / read the first column block of a [T, nC nM + 96] embed
+    matrix; the composed forward's copy into the block stands for its cat.
+    Then the whole op, forward + backward, both routes."""
+    import numpy as np
+
+    from spacy_ray_amd.ops import api as ops
+    from spacy_ray_amd.ops import torch_ref as ref
+
+    T, nC, nM, W = 1 << 20, 8, 64, 96
+    rng = np.random.default_rng(0)
+    p = 1.0 / np.arange(1, 27)
+    ids_np = 97 + rng.choice(26, size=(T, nC), p=p / p.sum())
+    other = rng.random((T, nC))
+    ids_np[other < 0.05] = rng.integers(0, 255, size=int((other < 0.05).sum()))
+    ids_np[rng.random((T, nC)) < 0.33] = 255
+    ids = torch.from_numpy(ids_np.astype(np.uint8)).to(dev)
+    E = (torch.randn(nC, 256, nM, device=dev) * 0.1).to(torch.bfloat16)
+    X = torch.zeros(T, nC * nM + W, device=dev, dtype=torch.bfloat16)
+    dX = (torch.randn(T, nC * nM + W, device=dev) * 0.1).to(torch.bfloat16)
+    block = dX[:, :nC * nM]
+    S, per = hip.char_embed_slices(T, nC)
+    io_bytes = T * nC * (nM * 2 + 1)
+    print(f"char_embed (T={T}, nC={nC}, nM={nM}, bf16, "
+          f"{float((ids == 255).float().mean()):.2f} of the cells 255, "
+          f"S={S} slices of {per} tokens):")
+
+    def composed_fwd():
+        X[:, :nC * nM] = ref.char_embed_forward(E, ids)
+
+    fwd = _alternate({"fused": lambda: hip.char_embed_fwd(E, ids, X, 0),
+                      "composed": composed_fwd})
+    for name, (med, mn) in fwd.items():
+        print(f"  fwd {name:9s} median {med:8.3f} ms  min {mn:8.3f} ms  "
+              f"{io_bytes / med / 1e9:8.3f} TB/s of the {io_bytes} floor bytes")
+    bwd = _alternate({
+        "fused": lambda: hip.char_embed_bwd(block, ids, nC, nM, False),
+        "determin.": lambda: hip.char_embed_bwd(block, ids, nC, nM, True),
+        "composed": lambda: ref.char_embed_backward(block, ids, nC, nM),
+    })
+    for name, (med, mn) in bwd.items():
+        print(f"  bwd {name:9s} median {med:8.3f} ms  min {mn:8.3f} ms  "
+              f"{io_bytes / med / 1e9:8.3f} TB/s of the {io_bytes} floor bytes")
+    diff = (hip.char_embed_bwd(block, ids, nC, nM, False).float()
+            - ref.char_embed_backward(block, ids, nC, nM).float()).abs().max().item()
+    print(f"  max |dE fused - composed| = {diff:.3e}")
+
+    table = (torch.randn(5000, W, device=dev) * 0.1).to(torch.bfloat16).requires_grad_(True)
+    Ep = E.clone().requires_grad_(True)
+    hash_ids = torch.from_numpy(rng.integers(1, 2 ** 62, size=(T, 4))).to(dev)[:, 0]
+
+    def step(mode):
+        def run():
+            os.environ["SRX_CHAR_EMBED"] = mode
+            ops.char_embed(Ep, ids, table, hash_ids, 5).backward(dX)
+            Ep.grad = table.grad = None
+        return run
+
+    routes = _alternate({"fused": step("fused"), "composed": step("composed")},
+                        iters=10, warmup=3)
+    os.environ.pop("SRX_CHAR_EMBED")
+    for name, (med, mn) in routes.items():
+        print(f"  op fwd+bwd {name:9s} median {med:8.3f} ms  min {mn:8.3f} ms")
+
+
 ALL = {"mwe": bench_mwe, "sparse_linear": bench_sparse_linear, "dpre": bench_dpre, "ce": bench_ce, "mixer": bench_mixer,
        "mwe_dw": bench_mwe_dw,
        "floret": bench_floret, "vecloss": bench_vecloss,
        "most_similar": bench_most_similar, "span_pool": bench_span_pool,
        "gpustate": bench_gpustate, "attn": bench_attn,
        "static_vectors": bench_static_vectors,
-       "hashembed": bench_hashembed}
+       "hashembed": bench_hashembed, "char_embed": bench_char_embed}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(ALL)
