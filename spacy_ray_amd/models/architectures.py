@@ -237,7 +237,8 @@ def make_textcat_reduce_model(tok2vec: ModelSpec,
     return spec
 
 
-def _textcat_bow_spec(name: str, ngram_size: int, length: int) -> ModelSpec:
+def _textcat_bow_spec(name: str, ngram_size: int, length: int,
+                      no_output_layer: bool = False) -> ModelSpec:
     ngram_size, length = int(ngram_size), int(length)
     if ngram_size < 1:
         raise ValueError(f"{name}: ngram_size must be >= 1, got {ngram_size}")
@@ -249,6 +250,9 @@ def _textcat_bow_spec(name: str, ngram_size: int, length: int) -> ModelSpec:
     # SparseLinear (ops.sparse_linear); TextcatPipe builds the head
     spec = ModelSpec(lambda: None, width=None, kind="textcat")
     spec.bow = {"ngram_size": ngram_size, "length": length}
+    # read by spacy.TextCatEnsemble.v2 alone; kept out of spec.bow, which a
+    # BOW pipe writes into its cfg
+    spec.no_output_layer = bool(no_output_layer)
     return spec
 
 
@@ -256,15 +260,48 @@ def _textcat_bow_spec(name: str, ngram_size: int, length: int) -> ModelSpec:
 def make_textcat_bow_v2(exclusive_classes: bool = True, ngram_size: int = 1,
                         no_output_layer: bool = False, nO: Optional[int] = None):
     """spaCy's efficiency-mode text classifier.  `no_output_layer` changes
-    nothing here: the softmax / sigmoid lives in the loss and in prediction."""
-    return _textcat_bow_spec("spacy.TextCatBOW.v2", ngram_size, 262144)
+    nothing here: the softmax / sigmoid lives in the loss and in prediction
+    (spacy.TextCatEnsemble.v2 honours it for its BOW branch)."""
+    return _textcat_bow_spec("spacy.TextCatBOW.v2", ngram_size, 262144, no_output_layer)
 
 
 @registry.architectures("spacy.TextCatBOW.v3")
 def make_textcat_bow_v3(exclusive_classes: bool = True, ngram_size: int = 1,
                         no_output_layer: bool = False, length: int = 262144,
                         nO: Optional[int] = None):
-    return _textcat_bow_spec("spacy.TextCatBOW.v3", ngram_size, length)
+    return _textcat_bow_spec("spacy.TextCatBOW.v3", ngram_size, length, no_output_layer)
+
+
+@registry.architectures("spacy.TextCatEnsemble.v2")
+def make_textcat_ensemble(tok2vec: ModelSpec, linear_model: ModelSpec,
+                          nO: Optional[int] = None):
+    """spaCy's accuracy-mode text classifier: a BOW branch (ops.sparse_linear,
+    through softmax / sigmoid unless its `no_output_layer` is set) next to
+    the tok2vec pooled by attention (ops.attention_pool) with a Maxout +
+    LayerNorm residual, concatenated into one output layer.  TextcatPipe
+    builds the head (TextcatEnsembleHead)."""
+    bow = getattr(linear_model, "bow", None)
+    if not isinstance(linear_model, ModelSpec) or bow is None:
+        raise ValueError(
+            "spacy.TextCatEnsemble.v2: linear_model must be a spacy.TextCatBOW.v2 "
+            f"or .v3 block, got {linear_model!r}")
+    spec = ModelSpec(lambda: None, width=tok2vec.width, kind="textcat")
+    spec.embedded_tok2vec = tok2vec if tok2vec.kind == "tok2vec" else None
+    spec.attention = {"keys": False, "bow": dict(bow),
+                      "no_output_layer": bool(linear_model.no_output_layer)}
+    return spec
+
+
+@registry.architectures("spacy.TextCatParametricAttention.v1")
+def make_textcat_parametric_attention(tok2vec: ModelSpec,
+                                      exclusive_classes: bool = True,
+                                      nO: Optional[int] = None):
+    """The ensemble's attention branch alone, with Thinc's Gelu(width ->
+    width) key transform in front of the attention, and an output layer."""
+    spec = ModelSpec(lambda: None, width=tok2vec.width, kind="textcat")
+    spec.embedded_tok2vec = tok2vec if tok2vec.kind == "tok2vec" else None
+    spec.attention = {"keys": True, "bow": None, "no_output_layer": False}
+    return spec
 
 
 @registry.layers("spacy.mean_max_reducer.v1")

@@ -869,6 +869,145 @@ def span_pool(X: torch.Tensor, index: SpanIndex, pad_rows: int = 1) -> torch.Ten
     return R
 
 
+# ------------------------------------------------------ attention pooling
+# Thinc's ParametricAttention + reduce_sum, the pooling of TextCatEnsemble
+# and TextCatParametricAttention.  attention_pool kernels
+# (srx_attnpool.hip.h: one read of X forward, one read of X and one write of
+# dX backward) against the composed path (torch_ref.attention_pool under
+# autograd: a GEMV, a segmented softmax by index ops, a broadcast multiply
+# into a new [T, W] and an index_add_).  Same rule as char_embed: a direction
+# is fused by default only where tools/kbench.py attention_pool measured it
+# not slower than composed on every shape (profiles/README.md);
+# SRX_ATTENTION_POOL=fused / composed overrides both directions.
+# Measured (T = 1M tokens, bf16, fused against composed, median ms):
+#   W =  96,  20-token docs: forward 0.169 / 1.788, backward 0.161 / 12.797
+#   W =  96, 400-token docs: forward 0.180 / 2.617, backward 0.185 / 12.797
+#   W =  96,  20-token docs, keys: forward 0.189 / 1.884, backward 0.217 / 12.772
+#   W = 768,  20-token docs: forward 0.485 / 6.336, backward 1.022 / 28.085
+#   W = 768, 400-token docs: forward 0.708 / 7.297, backward 1.105 / 27.939
+ATTENTION_POOL_FUSED_DEFAULT = {"fwd": True, "bwd": True}
+ATTENTION_POOL_MAX_W = 768
+ATTENTION_POOL_CHUNK = 64  # rows per work unit (SRX_ATTNPOOL_CHUNK)
+
+
+def _attention_pool_mode() -> str:
+    mode = os.environ.get("SRX_ATTENTION_POOL", "")
+    if mode not in ("", "fused", "composed"):
+        raise ValueError(
+            f"SRX_ATTENTION_POOL={mode!r}: expected 'fused' or 'composed'")
+    return mode
+
+
+def attention_pool_available(X: torch.Tensor, q: torch.Tensor,
+                             keys: Optional[torch.Tensor] = None) -> bool:
+    """The kernels take a contiguous bf16 (W % 8 == 0) or fp32 (W % 4 == 0) X
+    [T, W] on the GPU with W <= 768, keys of the same dtype, shape and
+    layout, and T < 2^31 - 64."""
+    if X.dim() != 2 or not X.is_cuda or not q.is_cuda:
+        return False
+    per = {torch.bfloat16: 8, torch.float32: 4}.get(X.dtype)
+    T, W = X.shape
+    return (
+        per is not None
+        and 0 < W <= ATTENTION_POOL_MAX_W
+        and W % per == 0
+        and T < 2 ** 31 - ATTENTION_POOL_CHUNK
+        and X.is_contiguous()
+        and (keys is None or (keys.is_cuda and keys.dtype == X.dtype
+                              and keys.shape == X.shape and keys.is_contiguous()))
+        and hip_ext() is not None
+    )
+
+
+class _AttentionPool(torch.autograd.Function):
+    """Forward: one launch over (doc, chunk) units and the merge of the long
+    docs' chunks; saves lse [D] and the fp32 P.  Backward: one pass that
+    writes dX (and dK) and the per-block dq rows, and their fixed-order sum;
+    no atomics.  A direction that is not fused runs torch_ref."""
+
+    @staticmethod
+    def forward(ctx, X, offsets, q, keys, rows, sub_wave, max_blocks, fwd, bwd):
+        q32 = q.detach().float().contiguous()
+        K = None if keys is None else keys.detach()
+        if fwd:
+            P, P32, lse, uo = hip_ext().attention_pool_fwd(
+                X.detach(), K, offsets, q32, rows, int(sub_wave), int(max_blocks))
+        else:
+            P, P32, lse = ref.attention_pool(X.detach(), offsets, q32, K,
+                                             with_state=True)
+            P = torch.cat([P, P.new_zeros(rows - P.shape[0], P.shape[1])])
+            P32, lse, uo = P32.float(), lse.float(), None
+        ctx.save_for_backward(X, offsets, q, keys, P32, lse, uo)
+        ctx.args = (int(sub_wave), int(max_blocks), bwd)
+        return P
+
+    @staticmethod
+    def backward(ctx, dP):
+        X, offsets, q, keys, P32, lse, uo = ctx.saved_tensors
+        sub_wave, max_blocks, bwd = ctx.args
+        D = offsets.numel() - 1
+        if bwd:
+            if uo is None:  # the forward was composed
+                uo = hip_ext().attention_pool_fwd(
+                    X.detach(), None if keys is None else keys.detach(), offsets,
+                    q.detach().float().contiguous(), D, sub_wave, max_blocks)[3]
+            dX, dK, dq = hip_ext().attention_pool_bwd(
+                X.detach(), None if keys is None else keys.detach(), offsets, uo,
+                q.detach().float().contiguous(), dP.contiguous(), P32, lse,
+                sub_wave, max_blocks)
+            return (dX, None, dq.to(q.dtype), dK if keys is not None else None,
+                    None, None, None, None, None)
+        with torch.enable_grad():
+            ins = [t.detach().requires_grad_(True)
+                   for t in (X, q) + (() if keys is None else (keys,))]
+            P = ref.attention_pool(ins[0], offsets, ins[1],
+                                   ins[2] if keys is not None else None)
+            grads = torch.autograd.grad(P, ins, dP[:D])
+        return (grads[0], None, grads[1], grads[2] if keys is not None else None,
+                None, None, None, None, None)
+
+
+def attention_pool(X: torch.Tensor, offsets: torch.Tensor, q: torch.Tensor,
+                   keys: Optional[torch.Tensor] = None, *, pad_rows: int = 1,
+                   sub_wave: int = 0, max_blocks: int = 0) -> torch.Tensor:
+    """Thinc's ParametricAttention followed by reduce_sum.  X [T, W]; doc d is
+    rows [offsets[d], offsets[d + 1]) with offsets int32 [D + 1] ascending
+    from 0 to T; q [W]; keys [T, W] or None (then keys = X).  s_t = keys_t .
+    q, a = softmax of s over the doc's rows, P[d] = sum_t a_t X[t]: [roundup(D,
+    pad_rows), W] in X's dtype, an empty doc and the pad rows zero, with
+    autograd to X, q and keys.  On a GPU, contiguous bf16 / fp32 input with W
+    <= 768 can run as the fused kernels (attention_pool_available): one read
+    of X forward, one read of X and one write of dX backward, atomic-free and
+    bit-reproducible; everything else takes torch_ref.attention_pool.
+    ATTENTION_POOL_FUSED_DEFAULT says which directions are fused by default,
+    SRX_ATTENTION_POOL=fused|composed overrides it.  sub_wave (0 / 8 / 16 /
+    32 / 64 lanes per row, raised until a lane owns at most 3 pieces of 16
+    bytes) and max_blocks > 0 (a cap on the grids) are for tests and
+    measurements; the result does not depend on max_blocks."""
+    if X.dim() != 2 or q.shape != (X.shape[1],):
+        raise ValueError("attention_pool: X must be [T, W] and q [W]")
+    if offsets.dim() != 1 or offsets.numel() < 1 or offsets.dtype != torch.int32:
+        raise ValueError("attention_pool: offsets must be int32 [D + 1]")
+    if keys is not None and keys.shape != X.shape:
+        raise ValueError("attention_pool: keys must have X's shape")
+    D = offsets.numel() - 1
+    pad_rows = max(1, int(pad_rows))
+    rows = (D + pad_rows - 1) // pad_rows * pad_rows
+    mode = _attention_pool_mode()  # a bad SRX_ATTENTION_POOL raises on every path
+    if X.is_cuda and mode != "composed":
+        _want_hip(X)  # a GPU run without the extension is an error, as elsewhere
+        if attention_pool_available(X, q, keys):
+            fwd = mode == "fused" or ATTENTION_POOL_FUSED_DEFAULT["fwd"]
+            bwd = mode == "fused" or ATTENTION_POOL_FUSED_DEFAULT["bwd"]
+            if fwd or bwd:
+                return _AttentionPool.apply(X, offsets.contiguous(), q, keys, rows,
+                                            sub_wave, max_blocks, fwd, bwd)
+    P = ref.attention_pool(X, offsets, q, keys)
+    if rows > D:
+        P = torch.cat([P, P.new_zeros(rows - D, P.shape[1])])
+    return P
+
+
 # ------------------------------------------------ SparseLinear (TextCatBOW)
 # sparse_linear kernels (srx_sparselinear.hip.h) against the composed path
 # (torch_ref.sparse_linear over ngram_buckets: an [2 nnz, nO] gather, a

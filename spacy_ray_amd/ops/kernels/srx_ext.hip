@@ -21,6 +21,7 @@
 #include "srx_floret.hip.h"
 #include "srx_vecloss.hip.h"
 #include "srx_spanpool.hip.h"
+#include "srx_attnpool.hip.h"
 #include "srx_sparselinear.hip.h"
 #include "srx_charembed.hip.h"
 #include "srx_activations.hip.h"
@@ -2063,6 +2064,193 @@ at::Tensor span_pool_bwd(at::Tensor dR, at::Tensor which, at::Tensor starts,
 }
 #undef SRX_SPANPOOL_DISPATCH
 
+// -------------------------------------------------------- attention pooling
+// see srx_attnpool.hip.h.  X (and keys) [T, W] bf16 (W % 8 == 0) or fp32 (W %
+// 4 == 0), W <= 768; offsets int32 [D + 1], ascending from 0 to T; q fp32 [W].
+namespace attnpool {
+
+struct Shape {
+  long T, W, D, V, bound, n_slots;
+  int sw, np;
+  bool bf16, hask;
+};
+
+inline Shape check(const at::Tensor& X, const c10::optional<at::Tensor>& keys,
+                   const at::Tensor& offsets, const at::Tensor& q, long sub_wave) {
+  Shape s;
+  s.V = spanpool::check_x(X, "attention_pool: X");
+  check_dev(offsets);
+  check_dev(q);
+  s.T = X.size(0), s.W = X.size(1), s.D = offsets.numel() - 1;
+  s.bf16 = X.scalar_type() == at::kBFloat16;
+  s.hask = keys.has_value();
+  TORCH_CHECK(s.W >= s.V && s.W % s.V == 0 && s.W <= SRX_ATTNPOOL_MAXW,
+              "attention_pool: W must be a multiple of ", s.V, " and <= ",
+              SRX_ATTNPOOL_MAXW);
+  TORCH_CHECK(offsets.scalar_type() == at::kInt && offsets.dim() == 1 && s.D >= 0,
+              "attention_pool: offsets must be int32 [D + 1]");
+  TORCH_CHECK(q.scalar_type() == at::kFloat && q.dim() == 1 && q.numel() == s.W,
+              "attention_pool: q must be fp32 [W]");
+  TORCH_CHECK(aligned16(X.data_ptr()) && aligned16(q.data_ptr()),
+              "attention_pool: X or q not 16-byte aligned");
+  if (s.hask) {
+    check_dev(*keys);
+    TORCH_CHECK(keys->scalar_type() == X.scalar_type() && keys->sizes() == X.sizes() &&
+                    aligned16(keys->data_ptr()),
+                "attention_pool: keys must match X in dtype and shape");
+  }
+  s.bound = s.D + s.T / SRX_ATTNPOOL_CHUNK;
+  s.n_slots = 2 * (s.T / SRX_ATTNPOOL_CHUNK);
+  TORCH_CHECK(s.T < (1L << 31) - SRX_ATTNPOOL_CHUNK && s.bound < (1L << 30),
+              "attention_pool: T and D + T / 64 must fit in int32");
+  TORCH_CHECK(sub_wave == 0 || sub_wave == 8 || sub_wave == 16 || sub_wave == 32 ||
+                  sub_wave == 64,
+              "attention_pool: sub_wave must be 0, 8, 16, 32 or 64");
+  const long Q = s.W / s.V;
+  s.sw = sub_wave ? (int)sub_wave : spanpool::sub_wave(Q);
+  while (3L * s.sw < Q) s.sw *= 2;  // a lane owns at most 3 pieces
+  s.np = (int)((Q + s.sw - 1) / s.sw);
+  return s;
+}
+
+inline dim3 grid_for(long units, long max_blocks) {
+  long cap = 8L * at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  if (max_blocks > 0) cap = max_blocks;
+  const long blocks = (units + SRX_ATTNPOOL_UNITS - 1) / SRX_ATTNPOOL_UNITS;
+  return dim3((unsigned)std::max<long>(1, std::min<long>(blocks, cap)));
+}
+
+template <int N>
+using ic = std::integral_constant<int, N>;
+
+// f(T{}, ic<SW>{}, ic<NP>{}, bool_constant<HASK>{}) for the shape's variant
+template <typename F>
+void dispatch(const Shape& s, F&& f) {
+#define SRX_AP_CASE(SW, NP)                                                    \
+  if (s.sw == SW && s.np == NP) {                                              \
+    if (s.bf16) {                                                              \
+      if (s.hask) f(bf16_t{}, ic<SW>{}, ic<NP>{}, std::true_type{});           \
+      else f(bf16_t{}, ic<SW>{}, ic<NP>{}, std::false_type{});                 \
+    } else {                                                                   \
+      if (s.hask) f(float{}, ic<SW>{}, ic<NP>{}, std::true_type{});            \
+      else f(float{}, ic<SW>{}, ic<NP>{}, std::false_type{});                  \
+    }                                                                          \
+    return;                                                                    \
+  }
+  SRX_AP_CASE(8, 1) SRX_AP_CASE(8, 2) SRX_AP_CASE(8, 3)
+  SRX_AP_CASE(16, 1) SRX_AP_CASE(16, 2) SRX_AP_CASE(16, 3)
+  SRX_AP_CASE(32, 1) SRX_AP_CASE(32, 2) SRX_AP_CASE(32, 3)
+  SRX_AP_CASE(64, 1) SRX_AP_CASE(64, 2) SRX_AP_CASE(64, 3)
+#undef SRX_AP_CASE
+  TORCH_CHECK(false, "attention_pool: no kernel variant");
+}
+
+}  // namespace attnpool
+
+// -> (P [rows, W], P32 fp32 [D, W], lse fp32 [D], unit_offsets int32 [D + 1]);
+// rows >= D, rows [D, rows) of P zero.  sub_wave: 0 = the power of two >= W /
+// V, or 8 / 16 / 32 / 64 (raised until a lane owns at most 3 pieces);
+// max_blocks > 0 caps the grid.
+std::vector<at::Tensor> attention_pool_fwd(at::Tensor X, c10::optional<at::Tensor> keys,
+                                           at::Tensor offsets, at::Tensor q, long rows,
+                                           long sub_wave, long max_blocks) {
+  const auto s = attnpool::check(X, keys, offsets, q, sub_wave);
+  TORCH_CHECK(rows >= s.D && rows < (1L << 30), "attention_pool_fwd: D <= rows < 2^30");
+  auto f32 = X.options().dtype(at::kFloat);
+  auto P = at::empty({rows, s.W}, X.options());
+  auto P32 = at::empty({s.D, s.W}, f32);
+  auto lse = at::empty({s.D}, f32);
+  // units per doc: max(1, ceil(len / CH)) of the clamped lengths, as the kernel
+  // clamps them
+  auto o = offsets.clamp(0, s.T);
+  auto len = (o.slice(0, 1) - o.slice(0, 0, s.D)).clamp_min(0);
+  auto n = at::div(len + (SRX_ATTNPOOL_CHUNK - 1), SRX_ATTNPOOL_CHUNK, "floor").clamp_min(1);
+  auto uo = at::zeros({s.D + 1}, offsets.options());
+  if (s.D > 0) uo.slice(0, 1).copy_(at::cumsum(n, 0));
+  if (rows == 0) return {P, P32, lse, uo};
+  auto ws_ml = at::empty({s.n_slots, 2}, f32);
+  auto ws_acc = at::empty({s.n_slots, s.W}, f32);
+  const long n_units = s.bound + (rows - s.D);
+  const dim3 grid = attnpool::grid_for(n_units, max_blocks);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  attnpool::dispatch(s, [&](auto t, auto sw, auto np, auto hask) {
+    using TT = decltype(t);
+    hipLaunchKernelGGL(
+        (attention_pool_fwd_kernel<TT, decltype(sw)::value, decltype(np)::value,
+                                   decltype(hask)::value>),
+        grid, dim3(SRX_ATTNPOOL_THREADS), 0, stream, (const TT*)X.data_ptr(),
+        (const TT*)(keys ? keys->data_ptr() : nullptr), offsets.data_ptr<int>(),
+        uo.data_ptr<int>(), q.data_ptr<float>(), (TT*)P.data_ptr(),
+        P32.data_ptr<float>(), lse.data_ptr<float>(), ws_ml.data_ptr<float>(),
+        ws_acc.data_ptr<float>(), (int)s.D, (int)rows, (int)s.T, (int)s.W,
+        (int)s.bound, (int)s.n_slots);
+  });
+  if (s.n_slots > 0 && s.D > 0) {  // some doc may have more than one unit
+    const long wpb = SRX_ATTNPOOL_THREADS / SRX_WAVE;
+    const dim3 mgrid = attnpool::grid_for((s.D + wpb - 1) / wpb * SRX_ATTNPOOL_UNITS,
+                                          max_blocks);
+#define SRX_AP_MERGE(TT)                                                       \
+  hipLaunchKernelGGL((attention_pool_merge_kernel<TT>), mgrid,                 \
+                     dim3(SRX_ATTNPOOL_THREADS), 0, stream, uo.data_ptr<int>(),\
+                     ws_ml.data_ptr<float>(), ws_acc.data_ptr<float>(),        \
+                     (TT*)P.data_ptr(), P32.data_ptr<float>(),                 \
+                     lse.data_ptr<float>(), (int)s.D, (int)s.W, (int)s.n_slots)
+    if (s.bf16) SRX_AP_MERGE(bf16_t); else SRX_AP_MERGE(float);
+#undef SRX_AP_MERGE
+  }
+  return {P, P32, lse, uo};
+}
+
+// -> (dX [T, W], dK [T, W] or an empty tensor, dq fp32 [W]); every row of dX
+// (and dK) is written
+std::vector<at::Tensor> attention_pool_bwd(at::Tensor X, c10::optional<at::Tensor> keys,
+                                           at::Tensor offsets, at::Tensor uo,
+                                           at::Tensor q, at::Tensor dP, at::Tensor P32,
+                                           at::Tensor lse, long sub_wave,
+                                           long max_blocks) {
+  const auto s = attnpool::check(X, keys, offsets, q, sub_wave);
+  check_dev(uo);
+  check_dev(dP);
+  check_dev(P32);
+  check_dev(lse);
+  TORCH_CHECK(uo.scalar_type() == at::kInt && uo.dim() == 1 && uo.numel() == s.D + 1,
+              "attention_pool_bwd: unit_offsets must be int32 [D + 1]");
+  TORCH_CHECK(dP.scalar_type() == X.scalar_type() && dP.dim() == 2 &&
+                  dP.size(0) >= s.D && dP.size(1) == s.W && aligned16(dP.data_ptr()),
+              "attention_pool_bwd: dP must be [>= D, W] in X's dtype");
+  TORCH_CHECK(P32.scalar_type() == at::kFloat && P32.dim() == 2 && P32.size(0) == s.D &&
+                  P32.size(1) == s.W && lse.scalar_type() == at::kFloat &&
+                  lse.dim() == 1 && lse.numel() == s.D && aligned16(P32.data_ptr()),
+              "attention_pool_bwd: P32 must be fp32 [D, W] and lse fp32 [D]");
+  auto f32 = X.options().dtype(at::kFloat);
+  if (s.D == 0 || s.T == 0)
+    return {at::zeros_like(X), s.hask ? at::zeros_like(X) : at::empty({0}, X.options()),
+            at::zeros({s.W}, f32)};
+  auto dX = at::empty_like(X);
+  auto dK = s.hask ? at::empty_like(X) : at::empty({0}, X.options());
+  const long n_blocks = (s.bound + SRX_ATTNPOOL_UNITS - 1) / SRX_ATTNPOOL_UNITS;
+  auto dq_part = at::empty({n_blocks, s.W}, f32);
+  auto dq = at::empty({s.W}, f32);
+  const dim3 grid = attnpool::grid_for(s.bound, max_blocks);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  attnpool::dispatch(s, [&](auto t, auto sw, auto np, auto hask) {
+    using TT = decltype(t);
+    hipLaunchKernelGGL(
+        (attention_pool_bwd_kernel<TT, decltype(sw)::value, decltype(np)::value,
+                                   decltype(hask)::value>),
+        grid, dim3(SRX_ATTNPOOL_THREADS), 0, stream, (const TT*)X.data_ptr(),
+        (const TT*)(keys ? keys->data_ptr() : nullptr), offsets.data_ptr<int>(),
+        uo.data_ptr<int>(), q.data_ptr<float>(), (const TT*)dP.data_ptr(),
+        P32.data_ptr<float>(), lse.data_ptr<float>(), (TT*)dX.data_ptr(),
+        (TT*)(s.hask ? dK.data_ptr() : nullptr), dq_part.data_ptr<float>(), (int)s.D,
+        (int)s.T, (int)s.W, (int)s.bound);
+  });
+  hipLaunchKernelGGL(attention_pool_dq_kernel, dim3((unsigned)((s.W + 15) / 16)),
+                     dim3(SRX_ATTNPOOL_THREADS), 0, stream, dq_part.data_ptr<float>(),
+                     dq.data_ptr<float>(), (int)n_blocks, (int)s.W);
+  return {dX, dK, dq};
+}
+
 // ------------------------------------------------- SparseLinear (TextCatBOW)
 // see srx_sparselinear.hip.h.  ids int64 [T], offsets int32 [D + 1], weight
 // bf16 / fp32 [L, nO], L a power of two <= 2^24, nO <= 128, G <= 4.
@@ -2524,6 +2712,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("span_pool_bwd", &span_pool_bwd, py::arg("dR"), py::arg("which"),
         py::arg("starts"), py::arg("ends"), py::arg("tok_offsets"),
         py::arg("tok_spans"));
+  m.def("attention_pool_fwd", &attention_pool_fwd, py::arg("X"), py::arg("keys"),
+        py::arg("offsets"), py::arg("q"), py::arg("rows"), py::arg("sub_wave") = 0,
+        py::arg("max_blocks") = 0);
+  m.def("attention_pool_bwd", &attention_pool_bwd, py::arg("X"), py::arg("keys"),
+        py::arg("offsets"), py::arg("unit_offsets"), py::arg("q"), py::arg("dP"),
+        py::arg("P32"), py::arg("lse"), py::arg("sub_wave") = 0,
+        py::arg("max_blocks") = 0);
+  m.attr("ATTENTION_POOL_CHUNK") = SRX_ATTNPOOL_CHUNK;
   m.def("ngram_buckets", &ngram_buckets, py::arg("ids"), py::arg("offsets"),
         py::arg("occ_offsets"), py::arg("nnz"), py::arg("ngram_size"),
         py::arg("length"));

@@ -199,6 +199,39 @@ def span_pool(X: torch.Tensor, starts: torch.Tensor, ends: torch.Tensor,
     return torch.cat(Rs), torch.cat(whichs)
 
 
+def attention_pool(X: torch.Tensor, offsets: torch.Tensor, q: torch.Tensor,
+                   keys: Optional[torch.Tensor] = None, with_state: bool = False):
+    """Thinc's ParametricAttention followed by reduce_sum.  X [T, W], doc d =
+    rows [offsets[d], offsets[d + 1]) (offsets ascending from 0 to T), q [W],
+    keys [T, W] (X when None): s = keys @ q, a = softmax of s within each doc,
+    P[d] = sum_t a_t X[t], [D, W] in X's dtype; an empty doc gives a zero
+    row.  Computed in fp32 (fp64 for fp64 input) and differentiable in X, q
+    and keys.  The softmax is segmented by index ops: a scatter-amax, an
+    index_add_ for the denominators and one for the weighted rows.
+    with_state also returns (the unrounded P, lse [D]), the state that the
+    kernels' backward takes (srx_attnpool.hip.h)."""
+    T, W = X.shape
+    D = offsets.numel() - 1
+    acc = torch.float64 if X.dtype == torch.float64 else torch.float32
+    o = offsets.long().clamp(0, T)
+    L = (o[1:] - o[:-1]).clamp(min=0)
+    doc_of = torch.repeat_interleave(torch.arange(D, device=X.device), L,
+                                     output_size=T)
+    Xa = X.to(acc)
+    s = (Xa if keys is None else keys.to(acc)) @ q.to(acc)
+    mx = torch.zeros(D, dtype=acc, device=X.device).scatter_reduce(
+        0, doc_of, s.detach(), "amax", include_self=False)
+    ex = torch.exp(s - mx[doc_of])
+    den = torch.zeros(D, dtype=acc, device=X.device).index_add_(0, doc_of, ex)
+    a = ex / den[doc_of]
+    P = torch.zeros(D, W, dtype=acc, device=X.device).index_add_(
+        0, doc_of, a[:, None] * Xa)
+    if with_state:
+        lse = mx + torch.log(den.detach().clamp(min=torch.finfo(acc).tiny))
+        return P.to(X.dtype), P.detach(), torch.where(L > 0, lse, 0.0)
+    return P.to(X.dtype)
+
+
 def ngram_counts(offsets: torch.Tensor, ngram_size: int) -> torch.Tensor:
     """int64 [D]: n-gram occurrences per doc, sum_n max(0, len - n + 1)."""
     lens = (offsets[1:] - offsets[:-1]).long()

@@ -1115,6 +1115,89 @@ class TextcatBowHead(nn.Module):
         return sparse_linear(ids, offsets, self.weight, self.bias, self.ngram_size)
 
 
+def _zero_linear(nI: int, nO: int) -> nn.Linear:
+    """An output layer that starts at zero, as TextcatHead's does."""
+    layer = nn.Linear(nI, nO)
+    nn.init.zeros_(layer.weight)
+    nn.init.zeros_(layer.bias)
+    return layer
+
+
+class AttentionResidual(nn.Module):
+    """Thinc's ParametricAttention >> reduce_sum >> residual(Maxout(width, 3
+    pieces) + LayerNorm), the block that spacy.TextCatEnsemble.v2 and
+    spacy.TextCatParametricAttention.v1 share.  Q starts at zero as in Thinc,
+    so attention starts uniform.  The pooling is ops.attention_pool; with
+    `keys` the attention scores keys = gelu(linear(X)) (Thinc's Gelu key
+    transform) and not X itself.  The Maxout + LayerNorm runs as the fused
+    mixer kernels where mixer_layer_available says so and as the composed
+    Maxout module otherwise."""
+
+    def __init__(self, width: int, keys: bool):
+        super().__init__()
+        from spacy_ray_amd.models.layers import Linear, Maxout
+
+        self.Q = nn.Parameter(torch.zeros(width))
+        self.key_transform = Linear(width, width) if keys else None
+        self.maxout = Maxout(width, width, 3, normalize=True)
+
+    def forward(self, X, offsets):
+        from spacy_ray_amd.ops import api as ops
+
+        keys = None
+        if self.key_transform is not None:
+            kt = self.key_transform
+            keys = ops.gelu(ops.linear_cdw(X, kt.weight, kt.bias))
+        R = ops.attention_pool(X, offsets, self.Q, keys, pad_rows=64)
+        m = self.maxout
+        if ops.mixer_layer_available(R, m.nO, m.pieces):
+            H = ops.mixer_layer(R, m.weight, m.bias, m.norm.weight,
+                                m.norm.bias, None, m.norm.eps)
+        else:
+            H = m(R)
+        return (R + H)[:offsets.numel() - 1]
+
+
+class TextcatAttentionHead(nn.Module):
+    """spacy.TextCatParametricAttention.v1: AttentionResidual with the key
+    transform, then the output layer (zero-initialised like TextcatHead)."""
+
+    def __init__(self, width: int, n_cats: int):
+        super().__init__()
+        self.attend = AttentionResidual(width, keys=True)
+        self.output = _zero_linear(width, n_cats)
+
+    def forward(self, X, offsets, n_docs):
+        from spacy_ray_amd.ops.api import linear_cdw
+
+        return linear_cdw(self.attend(X, offsets)[:n_docs], self.output.weight,
+                          self.output.bias)
+
+
+class TextcatEnsembleHead(nn.Module):
+    """spacy.TextCatEnsemble.v2: scores = Output(concat(bow [D, n_cats], cnn
+    [D, width])).  The BOW branch goes through its softmax (exclusive) or
+    sigmoid first unless no_output_layer is set, as in spaCy."""
+
+    def __init__(self, width: int, n_cats: int, bow: Dict, exclusive: bool,
+                 no_output_layer: bool):
+        super().__init__()
+        self.exclusive, self.no_output_layer = exclusive, no_output_layer
+        self.bow = TextcatBowHead(bow["length"], n_cats, bow["ngram_size"])
+        self.attend = AttentionResidual(width, keys=False)
+        self.output = _zero_linear(n_cats + width, n_cats)
+
+    def forward(self, X, offsets, n_docs, ids, bow_offsets):
+        from spacy_ray_amd.ops.api import linear_cdw
+
+        cnn = self.attend(X, offsets)[:n_docs]
+        bow = self.bow(ids, bow_offsets)
+        if not self.no_output_layer:
+            bow = torch.softmax(bow, dim=-1) if self.exclusive else torch.sigmoid(bow)
+        return linear_cdw(torch.cat([bow.to(cnn.dtype), cnn], dim=1),
+                          self.output.weight, self.output.bias)
+
+
 class TextcatPipe(TrainablePipe):
     """Doc-level classification over mean-pooled tok2vec (the reference is
     a generic spaCy trainer — `spacy ray train` accepts textcat configs,
@@ -1144,9 +1227,19 @@ class TextcatPipe(TrainablePipe):
         self.bow = getattr(spec, "bow", None)
         if self.bow is not None:
             self.listens_to = None
+        # spacy.TextCatEnsemble.v2 / TextCatParametricAttention.v1: {"keys",
+        # "bow", "no_output_layer"}; listens to the tok2vec, and the ensemble
+        # stages the BOW inputs as well
+        self.attention = getattr(spec, "attention", None)
 
     def _build_head(self, device):
         n = max(1, len(self.labels))
+        att = self.attention
+        if att is not None and att["bow"] is not None:
+            return TextcatEnsembleHead(self.width, n, att["bow"], self.exclusive,
+                                       att["no_output_layer"]).to(device)
+        if att is not None:
+            return TextcatAttentionHead(self.width, n).to(device)
         if self.bow is not None:
             return TextcatBowHead(self.bow["length"], n, self.bow["ngram_size"]).to(device)
         return TextcatHead(self.width, n).to(device)
@@ -1163,6 +1256,8 @@ class TextcatPipe(TrainablePipe):
         self.cfg["exclusive"] = self.exclusive
         if self.bow is not None:
             self.cfg.update(self.bow)
+        if self.attention is not None:
+            self.cfg["attention"] = self.attention
         if self.module is None:
             self.module = self._build_head(device)
         self._attach_embedded(device)
@@ -1174,6 +1269,8 @@ class TextcatPipe(TrainablePipe):
         self.exclusive = bool(cfg.get("exclusive", True))
         if self.bow is not None:  # rebuild the head that was saved
             self.bow = {k: int(cfg.get(k, self.bow[k])) for k in ("ngram_size", "length")}
+        if self.attention is not None:
+            self.attention = dict(cfg.get("attention", self.attention))
         if self.module is None:
             self.module = self._build_head(device)
         self._attach_embedded(device)
@@ -1192,7 +1289,7 @@ class TextcatPipe(TrainablePipe):
                else np.zeros(0, dtype=np.uint64)).astype(np.uint64, copy=False)
         offsets = np.zeros(len(docs) + 1, dtype=np.int32)
         np.cumsum([len(p) for p in parts], out=offsets[1:])
-        device = self.module.weight.device
+        device = next(self.module.parameters()).device
         staged = (to_device(ids.view(np.int64), device), to_device(offsets, device))
         if batch is not None:
             batch.staged[key] = staged
@@ -1210,6 +1307,15 @@ class TextcatPipe(TrainablePipe):
             lengths = torch.as_tensor(lens, dtype=torch.int64,
                                       device=t2v.device)
             total = sum(lens)
+        if self.attention is not None:
+            # lengths may include the batch's pad pseudo-doc: its row is
+            # pooled like any other and dropped by the head
+            offsets = torch.zeros(lengths.numel() + 1, dtype=torch.int32,
+                                  device=t2v.device)
+            offsets[1:] = torch.cumsum(lengths, 0)
+            extra = (self._bow_inputs(batch, docs)
+                     if self.attention["bow"] is not None else ())
+            return self.module(t2v[:total], offsets, len(docs), *extra)
         pooled = _ops.reduce_mean_ragged(t2v[:total], lengths)
         # TokenBatch may append a PAD pseudo-doc (GEMM shape bucketing)
         return self.module(pooled[:len(docs)])

@@ -847,6 +847,59 @@ def bench_span_pool():
         print(f"  head + loss fwd+bwd {name:9s} median {med:8.3f} ms  min {mn:8.3f} ms")
 
 
+def bench_attention_pool():
+    """attention_pool (srx_attnpool.hip.h) against the composed path
+    (torch_ref.attention_pool and its autograd backward) on the same inputs:
+    T = 1,048,576 tokens as 20-token and as 400-token docs, bf16, W = 96 and
+    768, without keys (the ensemble) and, at W = 96, with keys (parametric
+    attention).  Forward and backward are timed separately, whole calls."""
+    from spacy_ray_amd.ops import torch_ref as ref
+
+    T = 1 << 20
+    for W, doc, keys in ((96, 20, False), (96, 400, False), (96, 20, True),
+                         (768, 20, False), (768, 400, False)):
+        bounds = list(range(0, T, doc)) + [T]
+        offsets = torch.tensor(bounds, dtype=torch.int32, device=dev)
+        D = len(bounds) - 1
+        X = torch.randn(T, W, device=dev).to(torch.bfloat16)
+        K = torch.randn(T, W, device=dev).to(torch.bfloat16) if keys else None
+        q = torch.randn(W, device=dev) / W ** 0.5
+        dP = torch.randn(D, W, device=dev).to(torch.bfloat16)
+        rw = 2 if keys else 1
+        fwd_bytes = rw * T * W * 2 + D * W * 6
+        bwd_bytes = 2 * rw * T * W * 2 + D * W * 6
+        print(f"attention_pool (T={T}, W={W}, bf16, {D} docs of {doc} tokens, "
+              f"keys={keys}):")
+
+        P, P32, lse, uo = hip.attention_pool_fwd(X, K, offsets, q, D)
+        fwd = _alternate({
+            "fused": lambda: hip.attention_pool_fwd(X, K, offsets, q, D),
+            "composed": lambda: ref.attention_pool(X, offsets, q, K),
+        })
+        for name, (med, mn) in fwd.items():
+            print(f"  fwd {name:9s} median {med:8.3f} ms  min {mn:8.3f} ms  "
+                  f"{fwd_bytes / med / 1e9:8.3f} TB/s of the {fwd_bytes} floor bytes")
+
+        ins = [t.clone().requires_grad_(True) for t in ((X, q, K) if keys else (X, q))]
+        Pc = ref.attention_pool(ins[0], offsets, ins[1], ins[2] if keys else None)
+
+        def composed_bwd():
+            return torch.autograd.grad(Pc, ins, dP, retain_graph=True)
+
+        def fused_bwd():
+            return hip.attention_pool_bwd(X, K, offsets, uo, q, dP, P32, lse)
+
+        diff = (fused_bwd()[0].float() - composed_bwd()[0].float()).abs().max().item()
+        bwd = _alternate({"fused": fused_bwd, "composed": composed_bwd})
+        for name, (med, mn) in bwd.items():
+            print(f"  bwd {name:9s} median {med:8.3f} ms  min {mn:8.3f} ms  "
+                  f"{bwd_bytes / med / 1e9:8.3f} TB/s of the {bwd_bytes} floor bytes")
+        print(f"  max |P fused - composed| = "
+              f"{(P.float() - Pc.float()).abs().max().item():.3e}, "
+              f"max |dX fused - composed| = {diff:.3e}")
+        del Pc, ins, X, K, P, P32
+
+
 def bench_sparse_linear():
     """sparse_linear (srx_sparselinear.hip.h) against the composed path
     (ops.ngram_buckets + torch_ref.sparse_linear and its autograd backward)
@@ -988,7 +1041,7 @@ def bench_char_embed():
 ALL = {"mwe": bench_mwe, "sparse_linear": bench_sparse_linear, "dpre": bench_dpre, "ce": bench_ce, "mixer": bench_mixer,
        "mwe_dw": bench_mwe_dw,
        "floret": bench_floret, "vecloss": bench_vecloss,
-       "most_similar": bench_most_similar, "span_pool": bench_span_pool,
+       "most_similar": bench_most_similar, "span_pool": bench_span_pool, "attention_pool": bench_attention_pool,
        "gpustate": bench_gpustate, "attn": bench_attn,
        "static_vectors": bench_static_vectors,
        "hashembed": bench_hashembed, "char_embed": bench_char_embed}
