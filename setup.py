@@ -9,7 +9,10 @@ Two extensions:
   * spacy_ray_amd._srx_cpu — pybind11/C++ core (murmur hashing, transition
     systems).  Plain g++, no GPU needed.
   * spacy_ray_amd._srx_hip — CDNA4 (gfx950) HIP kernels as a torch extension;
-    hipcc cross-compiles on a GPU-less box (PYTORCH_ROCM_ARCH=gfx950).
+    hipcc cross-compiles on a GPU-less box (PYTORCH_ROCM_ARCH=gfx950).  Every
+    kernels/*.hip is one translation unit of it: srx_ext.hip (the module
+    block), one srx_bind_<family>.hip of launchers per kernel family,
+    srx_steploop.hip and srx_gpustate.hip.
   * spacy_ray_amd._srx_hip_vecsim — the cosine top-n kernels
     (srx_vecsim_ext.hip), compiled with packed fp32 instructions off.
 """

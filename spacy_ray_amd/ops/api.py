@@ -55,6 +55,33 @@ def _want_hip(t: torch.Tensor) -> bool:
     )
 
 
+def _env_mode(op: str, allowed=("fused", "composed")) -> str:
+    """SRX_<op>: "" when unset, else one of `allowed`; any other value is a
+    ValueError.  Callers ask before any early return, so a bad value raises
+    on every path, CPU tensors included."""
+    var = "SRX_" + op
+    mode = os.environ.get(var, "")
+    if mode and mode not in allowed:
+        want = " or ".join(repr(a) for a in allowed)
+        raise ValueError(f"{var}={mode!r}: expected {want} or unset")
+    return mode
+
+
+def _fused(op: str, probe: torch.Tensor, available, default: bool) -> bool:
+    """The SRX_<op>=fused|composed gate of an op with a fused kernel and a
+    composed path: False for `composed` and for a CPU `probe`; on the GPU a
+    missing extension is an error, as elsewhere; then the op's `available()`
+    must hold, and `fused` or the op's measured `default` decides.  Ops with
+    a default per direction ask once per direction."""
+    mode = _env_mode(op)
+    if mode == "composed" or not probe.is_cuda:
+        return False
+    _want_hip(probe)
+    if not available():
+        return False
+    return mode == "fused" or default
+
+
 # --------------------------------------------------------------- seq2col
 def boundary_masks_u8(lengths: torch.Tensor, total: int):
     """(is_start, is_end) uint8 device tensors — computed once per batch
@@ -127,10 +154,7 @@ def _hashembed_legacy() -> bool:
     """SRX_HASHEMBED=legacy: the per-table forward launches and the
     per-destination (4T-entry) sorted backward, for comparison and as an
     escape hatch."""
-    mode = os.environ.get("SRX_HASHEMBED", "")
-    if mode not in ("", "legacy"):
-        raise ValueError(f"SRX_HASHEMBED={mode!r}: expected 'legacy' or unset")
-    return mode == "legacy"
+    return _env_mode("HASHEMBED", ("legacy",)) == "legacy"
 
 
 def _multi_fwd_ok(ids4: torch.Tensor, tables) -> bool:
@@ -342,16 +366,8 @@ def static_vectors_available(table: torch.Tensor, W: torch.Tensor) -> bool:
 
 
 def _static_vectors_fused(table: torch.Tensor, W: torch.Tensor) -> bool:
-    mode = os.environ.get("SRX_STATIC_VECTORS", "")
-    if mode not in ("", "fused", "composed"):
-        raise ValueError(
-            f"SRX_STATIC_VECTORS={mode!r}: expected 'fused' or 'composed'")
-    if mode == "composed" or not W.is_cuda:
-        return False
-    _want_hip(W)  # a GPU run without the extension is an error, as elsewhere
-    if not static_vectors_available(table, W):
-        return False
-    return mode == "fused" or STATIC_VECTORS_FUSED_DEFAULT
+    return _fused("STATIC_VECTORS", W, lambda: static_vectors_available(table, W),
+                  STATIC_VECTORS_FUSED_DEFAULT)
 
 
 def _rows_i32(rows: torch.Tensor) -> torch.Tensor:
@@ -461,14 +477,6 @@ def multi_hashembed_vectors(ids4: torch.Tensor, seeds, tables,
 CHAR_EMBED_FUSED_DEFAULT = {"fwd": True, "bwd": True}
 
 
-def _char_embed_mode() -> str:
-    mode = os.environ.get("SRX_CHAR_EMBED", "")
-    if mode not in ("", "fused", "composed"):
-        raise ValueError(
-            f"SRX_CHAR_EMBED={mode!r}: expected 'fused' or 'composed'")
-    return mode
-
-
 def char_embed_available(E: torch.Tensor, ids: torch.Tensor,
                          hash_table: torch.Tensor) -> bool:
     """The fused kernels' fast path: bf16 or fp32 tables of one dtype on the
@@ -565,15 +573,12 @@ def char_embed(E: torch.Tensor, ids: torch.Tensor, hash_table: torch.Tensor,
                hash_ids: torch.Tensor, seed: int) -> torch.Tensor:
     """E [nC, 256, nM], ids uint8 [T, nC], one HashEmbed table [R, W] over
     hash_ids int64 [T] -> X [T, nC nM + W], the byte block first."""
-    mode = _char_embed_mode()  # a bad SRX_CHAR_EMBED raises on every path
-    if E.is_cuda and mode != "composed":
-        _want_hip(E)  # a GPU run without the extension is an error
-        if char_embed_available(E, ids, hash_table):
-            fwd = mode == "fused" or CHAR_EMBED_FUSED_DEFAULT["fwd"]
-            bwd = mode == "fused" or CHAR_EMBED_FUSED_DEFAULT["bwd"]
-            if fwd or bwd:
-                return _CharEmbed.apply(E, ids, hash_table, hash_ids, seed,
-                                        fwd, bwd)
+    # a bad SRX_CHAR_EMBED raises on every path
+    fwd, bwd = (_fused("CHAR_EMBED", E,
+                       lambda: char_embed_available(E, ids, hash_table),
+                       CHAR_EMBED_FUSED_DEFAULT[d]) for d in ("fwd", "bwd"))
+    if fwd or bwd:
+        return _CharEmbed.apply(E, ids, hash_table, hash_ids, seed, fwd, bwd)
     return torch.cat([_CharTable.apply(E, ids),
                       hashembed(hash_table, hash_ids.contiguous(), seed)], dim=1)
 
@@ -609,17 +614,11 @@ def floret_words_mean(table: torch.Tensor, offsets: torch.Tensor,
     dtype, row u = mean of table[idx[offsets[u] : offsets[u + 1]]].  The
     result is data (no autograd): it stands where the Vectors device table
     does in static_vectors / multi_hashembed."""
-    mode = os.environ.get("SRX_STATIC_VECTORS", "")
-    if mode not in ("", "fused", "composed"):
-        raise ValueError(
-            f"SRX_STATIC_VECTORS={mode!r}: expected 'fused' or 'composed'")
     table = table.detach()
-    fused = False
-    if mode != "composed" and table.is_cuda:
-        _want_hip(table)  # a GPU run without the extension is an error
-        fused = (floret_words_mean_available(table)
-                 and (mode == "fused" or FLORET_MEAN_FUSED_DEFAULT))
-    if not fused:
+    # the static-vectors switch, by design (see the comment above)
+    if not _fused("STATIC_VECTORS", table,
+                  lambda: floret_words_mean_available(table),
+                  FLORET_MEAN_FUSED_DEFAULT):
         with torch.no_grad():
             return ref.floret_words_mean(table, offsets, idx)
     offsets = _rows_i32(offsets).contiguous()
@@ -661,19 +660,6 @@ def vectors_loss_available(pred: torch.Tensor, table: torch.Tensor) -> bool:
     )
 
 
-def _vectors_loss_fused(pred: torch.Tensor, table: torch.Tensor) -> bool:
-    mode = os.environ.get("SRX_VECTORS_LOSS", "")
-    if mode not in ("", "fused", "composed"):
-        raise ValueError(
-            f"SRX_VECTORS_LOSS={mode!r}: expected 'fused' or 'composed'")
-    if mode == "composed" or not pred.is_cuda:
-        return False
-    _want_hip(pred)  # a GPU run without the extension is an error, as elsewhere
-    if not vectors_loss_available(pred, table):
-        return False
-    return mode == "fused" or VECTORS_LOSS_FUSED_DEFAULT
-
-
 class _VectorsLoss(torch.autograd.Function):
     """scale * sum_i loss_i; dPred is computed with the loss and kept for the
     backward, which only multiplies it by the incoming scalar.  The table is
@@ -681,7 +667,9 @@ class _VectorsLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, table, rows, loss, scale):
-        if _vectors_loss_fused(pred, table):
+        if _fused("VECTORS_LOSS", pred,
+                  lambda: vectors_loss_available(pred, table),
+                  VECTORS_LOSS_FUSED_DEFAULT):
             if pred.stride(1) != 1:
                 pred = pred.contiguous()
             rows = _rows_i32(rows).contiguous()
@@ -813,19 +801,6 @@ def span_pool_available(X: torch.Tensor, index: SpanIndex) -> bool:
     )
 
 
-def _span_pool_fused(X: torch.Tensor, index: SpanIndex) -> bool:
-    mode = os.environ.get("SRX_SPAN_POOL", "")
-    if mode not in ("", "fused", "composed"):
-        raise ValueError(
-            f"SRX_SPAN_POOL={mode!r}: expected 'fused' or 'composed'")
-    if mode == "composed" or not X.is_cuda:
-        return False
-    _want_hip(X)  # a GPU run without the extension is an error, as elsewhere
-    if not span_pool_available(X, index):
-        return False
-    return mode == "fused" or SPAN_POOL_FUSED_DEFAULT
-
-
 class _SpanPool(torch.autograd.Function):
     """Forward: one launch writes R (pad rows included) and `which`.
     Backward: one gather launch over the token rows, no atomics."""
@@ -861,7 +836,8 @@ def span_pool(X: torch.Tensor, index: SpanIndex, pad_rows: int = 1) -> torch.Ten
     S = index.n_spans
     pad_rows = max(1, int(pad_rows))
     rows = (S + pad_rows - 1) // pad_rows * pad_rows
-    if _span_pool_fused(X, index):
+    if _fused("SPAN_POOL", X, lambda: span_pool_available(X, index),
+              SPAN_POOL_FUSED_DEFAULT):
         return _SpanPool.apply(X, index, rows)
     R, _ = ref.span_pool(X, index.starts, index.ends, max_len=index.max_len)
     if rows > S:
@@ -888,14 +864,6 @@ def span_pool(X: torch.Tensor, index: SpanIndex, pad_rows: int = 1) -> torch.Ten
 ATTENTION_POOL_FUSED_DEFAULT = {"fwd": True, "bwd": True}
 ATTENTION_POOL_MAX_W = 768
 ATTENTION_POOL_CHUNK = 64  # rows per work unit (SRX_ATTNPOOL_CHUNK)
-
-
-def _attention_pool_mode() -> str:
-    mode = os.environ.get("SRX_ATTENTION_POOL", "")
-    if mode not in ("", "fused", "composed"):
-        raise ValueError(
-            f"SRX_ATTENTION_POOL={mode!r}: expected 'fused' or 'composed'")
-    return mode
 
 
 def attention_pool_available(X: torch.Tensor, q: torch.Tensor,
@@ -993,15 +961,13 @@ def attention_pool(X: torch.Tensor, offsets: torch.Tensor, q: torch.Tensor,
     D = offsets.numel() - 1
     pad_rows = max(1, int(pad_rows))
     rows = (D + pad_rows - 1) // pad_rows * pad_rows
-    mode = _attention_pool_mode()  # a bad SRX_ATTENTION_POOL raises on every path
-    if X.is_cuda and mode != "composed":
-        _want_hip(X)  # a GPU run without the extension is an error, as elsewhere
-        if attention_pool_available(X, q, keys):
-            fwd = mode == "fused" or ATTENTION_POOL_FUSED_DEFAULT["fwd"]
-            bwd = mode == "fused" or ATTENTION_POOL_FUSED_DEFAULT["bwd"]
-            if fwd or bwd:
-                return _AttentionPool.apply(X, offsets.contiguous(), q, keys, rows,
-                                            sub_wave, max_blocks, fwd, bwd)
+    # a bad SRX_ATTENTION_POOL raises on every path
+    fwd, bwd = (_fused("ATTENTION_POOL", X,
+                       lambda: attention_pool_available(X, q, keys),
+                       ATTENTION_POOL_FUSED_DEFAULT[d]) for d in ("fwd", "bwd"))
+    if fwd or bwd:
+        return _AttentionPool.apply(X, offsets.contiguous(), q, keys, rows,
+                                    sub_wave, max_blocks, fwd, bwd)
     P = ref.attention_pool(X, offsets, q, keys)
     if rows > D:
         P = torch.cat([P, P.new_zeros(rows - D, P.shape[1])])
@@ -1070,19 +1036,6 @@ def sparse_linear_available(ids: torch.Tensor, weight: torch.Tensor,
     )
 
 
-def _sparse_linear_fused(ids, weight, ngram_size) -> bool:
-    mode = os.environ.get("SRX_SPARSE_LINEAR", "")
-    if mode not in ("", "fused", "composed"):
-        raise ValueError(
-            f"SRX_SPARSE_LINEAR={mode!r}: expected 'fused' or 'composed'")
-    if mode == "composed" or not weight.is_cuda:
-        return False
-    _want_hip(weight)  # a GPU run without the extension is an error, as elsewhere
-    if not sparse_linear_available(ids, weight, ngram_size):
-        return False
-    return mode == "fused" or SPARSE_LINEAR_FUSED_DEFAULT
-
-
 class _SparseLinear(torch.autograd.Function):
     """Forward: one launch, hashing in registers.  Backward: the keys kernel,
     one sort, the chunked segmented reduce and its fix-up; no atomics."""
@@ -1131,7 +1084,9 @@ def sparse_linear(ids: torch.Tensor, offsets: torch.Tensor, weight: torch.Tensor
     _check_sparse_linear(ids, offsets, ngram_size, weight.shape[0])
     if weight.dim() != 2 or bias.shape != (weight.shape[1],):
         raise ValueError("sparse_linear: weight must be [L, nO] and bias [nO]")
-    if _sparse_linear_fused(ids, weight, ngram_size):
+    if _fused("SPARSE_LINEAR", weight,
+              lambda: sparse_linear_available(ids, weight, ngram_size),
+              SPARSE_LINEAR_FUSED_DEFAULT):
         return _SparseLinear.apply(ids.contiguous(), offsets.contiguous(), weight,
                                    bias, ngram_size, sub_wave, max_blocks)
     buckets = ngram_buckets(ids, offsets, ngram_size, weight.shape[0])
@@ -1188,22 +1143,17 @@ def vectors_most_similar_available(queries: torch.Tensor, table: torch.Tensor,
 
 
 def _vectors_most_similar_fused(queries, table, n) -> bool:
-    mode = os.environ.get("SRX_MOST_SIMILAR", "")
-    if mode not in ("", "fused", "composed"):
-        raise ValueError(
-            f"SRX_MOST_SIMILAR={mode!r}: expected 'fused' or 'composed'")
-    if mode == "composed" or not queries.is_cuda:
-        return False
-    # a GPU run without the extension is an error, as elsewhere
-    _want_hip(queries)
-    if hip_vecsim_ext() is None and os.environ.get("SRX_ALLOW_TORCH_FALLBACK") != "1":
-        raise RuntimeError(
-            "spacy_ray_amd._srx_hip_vecsim (gfx950 cosine top-n kernels) is not "
-            "built but vectors_most_similar ran on a GPU tensor. Build with "
-            "`python setup.py build_ext --inplace`.")
-    if not vectors_most_similar_available(queries, table, n):
-        return False
-    return mode == "fused" or VECTORS_MOST_SIMILAR_FUSED_DEFAULT
+    def available() -> bool:
+        # the kernels live in an extension module of their own
+        if hip_vecsim_ext() is None and os.environ.get("SRX_ALLOW_TORCH_FALLBACK") != "1":
+            raise RuntimeError(
+                "spacy_ray_amd._srx_hip_vecsim (gfx950 cosine top-n kernels) is not "
+                "built but vectors_most_similar ran on a GPU tensor. Build with "
+                "`python setup.py build_ext --inplace`.")
+        return vectors_most_similar_available(queries, table, n)
+
+    return _fused("MOST_SIMILAR", queries, available,
+                  VECTORS_MOST_SIMILAR_FUSED_DEFAULT)
 
 
 def vectors_row_inv(table: torch.Tensor) -> torch.Tensor:
@@ -1647,20 +1597,14 @@ class _MWELayer(torch.autograd.Function):
                 db32.to(dY.dtype), None, None, None, None)
 
 
-def _mwe_dw_composed() -> bool:
-    """SRX_MWE_DW=composed: dPre [T, 3W] + seq2col + the chunked library
-    GEMM for the MWE weight gradient, for comparison and as an escape hatch."""
-    mode = os.environ.get("SRX_MWE_DW", "")
-    if mode not in ("", "composed"):
-        raise ValueError(f"SRX_MWE_DW={mode!r}: expected 'composed' or unset")
-    return mode == "composed"
-
-
 def mwe_dw_available(width: int) -> bool:
     """Where the MWE backward takes mwe_bwd_dw: W = 96 (the 288 x 288 fp32
     accumulator fits one workgroup's registers; 384 x 384 at W = 128 does
-    not, docs/KERNELS.md)."""
-    composed = _mwe_dw_composed()  # a bad SRX_MWE_DW raises on every path
+    not, docs/KERNELS.md).  SRX_MWE_DW=composed: dPre [T, 3W] + seq2col + the
+    chunked library GEMM for the MWE weight gradient, for comparison and as
+    an escape hatch."""
+    # a bad SRX_MWE_DW raises on every path
+    composed = _env_mode("MWE_DW", ("composed",)) == "composed"
     return (not composed) and width == 96
 
 
@@ -1718,23 +1662,17 @@ def mixer_layer(E, weight, bias, g, b, dropmask=None, eps: float = 1e-5):
     return _MixerLayer.apply(E, weight, bias, g, b, dropmask, eps)
 
 
-def _mixer_composed() -> bool:
-    """SRX_MIXER=composed: the library GEMM + maxout + LayerNorm + dropout
-    chain, for comparison and as an escape hatch."""
-    mode = os.environ.get("SRX_MIXER", "")
-    if mode not in ("", "composed"):
-        raise ValueError(f"SRX_MIXER={mode!r}: expected 'composed' or unset")
-    return mode == "composed"
-
-
 def mixer_layer_available(E: torch.Tensor, width: int, pieces: int) -> bool:
     """Where MultiHashEmbed takes the fused mixer: bf16 on the GPU, 3
     pieces, W in {96, 128}, 4 input blocks of width W, T % 64 == 0.  The
     kernels also cover 5 blocks (include_static_vectors; it fits in LDS and
     is tested), but only the 4-block shape has been measured against the
     composed chain, and the fused path is the default only where it was
-    measured not slower (docs/KERNELS.md)."""
-    composed = _mixer_composed()  # a bad SRX_MIXER raises on every path
+    measured not slower (docs/KERNELS.md).  SRX_MIXER=composed: the library
+    GEMM + maxout + LayerNorm + dropout chain, for comparison and as an
+    escape hatch."""
+    # a bad SRX_MIXER raises on every path
+    composed = _env_mode("MIXER", ("composed",)) == "composed"
     return (
         not composed
         and E.is_cuda

@@ -865,9 +865,10 @@ __global__ __launch_bounds__(4 * W) void mwe_bwd_fused_kernel(
 // out[b, c] = sum over rows [b R, min((b+1) R, n)) of in[:, c], added in row
 // order in fp64 and rounded to fp32 once: the fixed-order reduction of the
 // per-tile column sums above (applied until one row is left).
-__global__ void mwe_colsum_kernel(const float* __restrict__ in,
-                                  float* __restrict__ out, long n, int R,
-                                  int ncols) {
+// `inline`: not a template, and this header reaches several translation units.
+inline __global__ void mwe_colsum_kernel(const float* __restrict__ in,
+                                         float* __restrict__ out, long n, int R,
+                                         int ncols) {
   const int c = blockIdx.y * blockDim.x + threadIdx.x;
   if (c >= ncols) return;
   const long r0 = (long)blockIdx.x * R;

@@ -341,9 +341,10 @@ __global__ __launch_bounds__(4 * NO) void static_vectors_bwd_dw_kernel(
 }
 
 // dW[o, k] = sum over g, in order, of ws[g, o, k]; drops the K padding
-__global__ void static_vectors_reduce_kernel(const float* __restrict__ ws,
-                                             float* __restrict__ dW, int G,
-                                             int NO, int nM, int nMp) {
+// `inline`: not a template, and this header reaches several translation units.
+inline __global__ void static_vectors_reduce_kernel(const float* __restrict__ ws,
+                                                    float* __restrict__ dW, int G,
+                                                    int NO, int nM, int nMp) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= NO * nM) return;
   const int o = idx / nM, k = idx - o * nM;

@@ -14,7 +14,7 @@
 // Training outputs land in device arenas (scores/gold/valid/feats/which/
 // hidden over ALL steps) so the loss + backward run BATCHED afterwards:
 // one fused CE kernel + 3 large GEMMs + one scatter for the whole loop
-// instead of per-step autograd nodes (replaces fusedstep:: in srx_ext.hip).
+// instead of per-step autograd nodes (replaces fusedstep:: in srx_bind_parser.hip).
 //
 // Contract mirrored from spaCy's parser_model.pyx step semantics
 // (SURVEY.md §2.2 N8); state machines via srx::StepBatchIface

@@ -304,7 +304,7 @@ class _TransitionTask:
         # fully-fused C++ step (scorer kernel + upper GEMM + action select in
         # ONE python call, backward entries stashed in a C++ store); default
         # on — GPU-validated vs the python path (test_fused_step_parity);
-        # SRX_FUSED_STEP=0 falls back.  See fusedstep in srx_ext.hip.
+        # SRX_FUSED_STEP=0 falls back.  See fusedstep in srx_bind_parser.hip.
         self.fused = (
             self.hip is not None
             and hasattr(self.hip, "fused_step")

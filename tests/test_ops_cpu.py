@@ -143,3 +143,88 @@ def test_activations_match_torch_builtins():
     api.mish(xa).sum().backward()
     F.mish(xb).sum().backward()
     assert torch.allclose(xa.grad, xb.grad, atol=1e-5)
+
+
+# ------------------------------------------------ SRX_<OP> environment gates
+_T, _W = 4, 8  # tokens, width; 2 docs of 2 tokens
+
+
+def _gate_static_vectors():
+    ops.static_vectors(torch.randn(_W, _W), torch.randn(5, _W),
+                       torch.tensor([0, 1, 2, 3]))
+
+
+def _gate_char_embed():
+    ops.char_embed(torch.randn(2, 256, _W),
+                   torch.zeros(_T, 2, dtype=torch.uint8), torch.randn(7, _W),
+                   torch.arange(_T, dtype=torch.int64), 1)
+
+
+def _gate_floret():
+    ops.floret_words_mean(torch.randn(5, _W),
+                          torch.tensor([0, 2, 4], dtype=torch.int32),
+                          torch.tensor([0, 1, 2, 3], dtype=torch.int32))
+
+
+def _gate_vectors_loss():
+    ops.vectors_loss(torch.randn(_T, _W), torch.randn(5, _W),
+                     torch.tensor([0, 1, 2, 3]))
+
+
+def _gate_span_pool():
+    ops.span_pool(torch.randn(_T, _W), ops.span_index([0, 1], [2, 4], _T, "cpu"))
+
+
+def _gate_attention_pool():
+    ops.attention_pool(torch.randn(_T, _W),
+                       torch.tensor([0, 2, 4], dtype=torch.int32),
+                       torch.randn(_W))
+
+
+def _gate_sparse_linear():
+    ops.sparse_linear(torch.arange(_T, dtype=torch.int64),
+                      torch.tensor([0, 2, 4], dtype=torch.int32),
+                      torch.randn(16, 3), torch.zeros(3))
+
+
+def _gate_most_similar():
+    ops.vectors_most_similar(torch.randn(2, _W), torch.randn(5, _W), 1)
+
+
+def _gate_hashembed():
+    # the HashEmbed gate sits on the GPU paths only; the fast-path test is
+    # the one caller that takes CPU tensors
+    ops._multi_fwd_ok(torch.arange(_T, dtype=torch.int64).view(-1, 1),
+                      [torch.randn(7, _W)])
+
+
+_GATES = [
+    ("SRX_HASHEMBED", _gate_hashembed, False),
+    ("SRX_STATIC_VECTORS", _gate_static_vectors, True),
+    ("SRX_STATIC_VECTORS", _gate_floret, True),
+    ("SRX_CHAR_EMBED", _gate_char_embed, True),
+    ("SRX_VECTORS_LOSS", _gate_vectors_loss, True),
+    ("SRX_SPAN_POOL", _gate_span_pool, True),
+    ("SRX_ATTENTION_POOL", _gate_attention_pool, True),
+    ("SRX_SPARSE_LINEAR", _gate_sparse_linear, True),
+    ("SRX_MOST_SIMILAR", _gate_most_similar, True),
+    ("SRX_MWE_DW", lambda: ops.mwe_dw_available(96), False),
+    ("SRX_MIXER",
+     lambda: ops.mixer_layer_available(torch.zeros(_T, 4 * _W), _W, 3), False),
+]
+
+
+@pytest.mark.parametrize(
+    "var,call,value",
+    [(var, call, value) for var, call, takes_fused in _GATES
+     for value in (("bogus",) if takes_fused else ("bogus", "fused"))],
+    ids=lambda p: p if isinstance(p, str) else getattr(p, "__name__", "call"))
+def test_env_gate_rejects_bad_value_on_cpu(monkeypatch, var, call, value):
+    """A value outside a gate's allowed set raises ValueError naming the
+    variable on the CPU path too; SRX_HASHEMBED, SRX_MWE_DW and SRX_MIXER do
+    not take 'fused'.  Unset, the same call goes through."""
+    monkeypatch.delenv(var, raising=False)
+    call()
+    monkeypatch.setenv(var, value)
+    with pytest.raises(ValueError, match=var):
+        call()
