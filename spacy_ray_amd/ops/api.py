@@ -1554,8 +1554,10 @@ class _MWELayer(torch.autograd.Function):
     (mask x layernorm_bwd x maxout scatter) and dX (dPre @ W, seq2col_bwd
     and the residual), then dW.  At W = 96 the fused kernel stores the compact
     dM [T, W] and mwe_bwd_dw (srx_mwe_dw.hip.h) computes dW from dM, `which`
-    and X; otherwise (W = 128, SRX_MWE_DW=composed) dPre [T, 3W] is written
-    and dW is the hipBLASLt GEMM on the recomputed seq2col."""
+    and X; otherwise (W = 128 or 256, SRX_MWE_DW=composed) dPre [T, 3W] is
+    written and dW is the hipBLASLt GEMM on the recomputed seq2col.  W = 256
+    runs the wide-row kernels of srx_mwe_wide.hip.h behind the same two
+    bindings."""
 
     @staticmethod
     def forward(ctx, X, weight, bias, g, b, starts, ends, dropmask, eps):
@@ -1613,11 +1615,14 @@ def mwe_layer(X, weight, bias, g, b, starts, ends, dropmask=None, eps: float = 1
 
 
 def mwe_layer_available(X: torch.Tensor, width: int, pieces: int) -> bool:
+    """Where MaxoutWindowEncoder takes the fused block: bf16 on the GPU,
+    three maxout pieces, T padded to 64, and width 96, 128 (srx_mwe.hip.h)
+    or 256 (srx_mwe_wide.hip.h, spaCy's accuracy preset)."""
     return (
         X.is_cuda
         and X.dtype == torch.bfloat16
         and pieces == 3
-        and width in (96, 128)
+        and width in (96, 128, 256)
         and X.shape[0] % 64 == 0
         and hip_ext() is not None
     )

@@ -3,6 +3,7 @@
 #include "srx_bind.hip.h"
 
 #include "srx_mwe.hip.h"
+#include "srx_mwe_wide.hip.h"
 #include "srx_mixer.hip.h"
 #include "srx_mwe_dw.hip.h"
 
@@ -110,6 +111,37 @@ void launch_mwe(const at::Tensor& X, const at::Tensor& Wt, const at::Tensor& bia
                      mu.data_ptr<float>(), rstd.data_ptr<float>(), T, (float)eps);
 }
 
+// W = 256: 64 whole rows per workgroup (srx_mwe_wide.hip.h)
+void launch_mwe_wide(const at::Tensor& X, const at::Tensor& Wt,
+                     const at::Tensor& bias, const at::Tensor& g,
+                     const at::Tensor& b, const at::Tensor& starts,
+                     const at::Tensor& ends,
+                     const c10::optional<at::Tensor>& dropmask, at::Tensor& Y,
+                     at::Tensor& Mout, at::Tensor& which, at::Tensor& mu,
+                     at::Tensor& rstd, long T, double eps, hipStream_t stream) {
+  using C = MweWideFwdCfg;
+  // X halo image + double-buffered B chunks (the epilogue tiles reuse the
+  // B region): 154 KB -> one 8-wave workgroup per CU
+  size_t lds_bytes = C::LDS_BYTES;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)mwe_wide_fwd_kernel<256>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_bytes);
+    attr_set = true;
+  }
+  dim3 grid((unsigned)((T + C::MT - 1) / C::MT));
+  hipLaunchKernelGGL((mwe_wide_fwd_kernel<256>), grid, dim3(C::NT), lds_bytes,
+                     stream, (const bf16_t*)X.data_ptr(), (const bf16_t*)Wt.data_ptr(),
+                     (const bf16_t*)bias.data_ptr(), (const bf16_t*)g.data_ptr(),
+                     (const bf16_t*)b.data_ptr(), starts.data_ptr<uint8_t>(),
+                     ends.data_ptr<uint8_t>(),
+                     dropmask ? (const bf16_t*)dropmask->data_ptr() : nullptr,
+                     (bf16_t*)Y.data_ptr(),
+                     (bf16_t*)Mout.data_ptr(), which.data_ptr<uint8_t>(),
+                     mu.data_ptr<float>(), rstd.data_ptr<float>(), T, (float)eps);
+}
+
 std::vector<at::Tensor> mwe_layer_fwd(at::Tensor X, at::Tensor Wt, at::Tensor bias,
                                       at::Tensor g, at::Tensor b, at::Tensor starts,
                                       at::Tensor ends,
@@ -118,7 +150,8 @@ std::vector<at::Tensor> mwe_layer_fwd(at::Tensor X, at::Tensor Wt, at::Tensor bi
   TORCH_CHECK(X.scalar_type() == at::kBFloat16, "mwe_layer is bf16-only");
   long T = X.size(0);
   int W = (int)X.size(1);
-  TORCH_CHECK(W == 96 || W == 128, "mwe_layer supports W in {96,128}");
+  TORCH_CHECK(W == 96 || W == 128 || W == 256,
+              "mwe_layer supports W in {96,128,256}");
   TORCH_CHECK(T % 64 == 0, "mwe_layer needs T % 64 == 0 (TokenBatch pads)");
   TORCH_CHECK(Wt.size(0) == 3 * W && Wt.size(1) == 3 * W, "weight must be [3W,3W]");
   auto Y = at::empty_like(X);
@@ -131,6 +164,9 @@ std::vector<at::Tensor> mwe_layer_fwd(at::Tensor X, at::Tensor Wt, at::Tensor bi
     if (W == 96)
       launch_mwe<96>(X, Wt, bias, g, b, starts, ends, dropmask, Y, Mout, which, mu,
                      rstd, T, eps, stream);
+    else if (W == 256)
+      launch_mwe_wide(X, Wt, bias, g, b, starts, ends, dropmask, Y, Mout, which,
+                      mu, rstd, T, eps, stream);
     else
       launch_mwe<128>(X, Wt, bias, g, b, starts, ends, dropmask, Y, Mout, which, mu,
                       rstd, T, eps, stream);
@@ -229,6 +265,39 @@ void launch_mwe_bwd_fused(const at::Tensor& dY,
                      partials.data_ptr<float>(), T);
 }
 
+// W = 256: compact dM + tag bytes in LDS, the A fragment of each piece
+// formed in registers (srx_mwe_wide.hip.h)
+void launch_mwe_wide_bwd_fused(const at::Tensor& dY,
+                               const c10::optional<at::Tensor>& dropmask,
+                               const at::Tensor& Mout, const at::Tensor& g,
+                               const at::Tensor& mu, const at::Tensor& rstd,
+                               const at::Tensor& which, const at::Tensor& WT,
+                               const at::Tensor& starts, const at::Tensor& ends,
+                               at::Tensor& dPre, at::Tensor& dX,
+                               at::Tensor& partials, long T, hipStream_t stream) {
+  using C = MweWideBwdCfg;
+  // dM halo image + tag bytes + double-buffered B chunks: 142 KB -> one
+  // 8-wave workgroup per CU
+  size_t lds_bytes = C::LDS_BYTES;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)mwe_wide_bwd_fused_kernel<256>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_bytes);
+    attr_set = true;
+  }
+  dim3 grid((unsigned)((T + C::MT - 1) / C::MT));
+  hipLaunchKernelGGL((mwe_wide_bwd_fused_kernel<256>), grid, dim3(C::NT), lds_bytes,
+                     stream, (const bf16_t*)dY.data_ptr(),
+                     dropmask ? (const bf16_t*)dropmask->data_ptr() : nullptr,
+                     (const bf16_t*)Mout.data_ptr(), (const bf16_t*)g.data_ptr(),
+                     mu.data_ptr<float>(), rstd.data_ptr<float>(),
+                     which.data_ptr<uint8_t>(), (const bf16_t*)WT.data_ptr(),
+                     starts.data_ptr<uint8_t>(), ends.data_ptr<uint8_t>(),
+                     (bf16_t*)dPre.data_ptr(), (bf16_t*)dX.data_ptr(),
+                     partials.data_ptr<float>(), T);
+}
+
 // mwe_bwd_stage1 + mwe_bwd_dx in one kernel: dPre is computed per 128-row
 // tile straight into the dX GEMM's LDS image and written to memory once
 // (for the dW GEMM), never read back.  The column sums leave as one fp32
@@ -236,7 +305,8 @@ void launch_mwe_bwd_fused(const at::Tensor& dY,
 // kernel serves SRX_DETERMINISTIC.  Returns {dPre, dX, dg32, db32, dbias32}.
 // compact: the first output is dM [T, W] (dPre[t, which[t,c] W + c], the
 // input of mwe_bwd_dw) instead of the expanded dPre [T, 3W]; the others are
-// bit-identical.
+// bit-identical.  W = 256 has no compact form (there is no dW kernel at that
+// width to read it).
 std::vector<at::Tensor> mwe_bwd_fused(at::Tensor dY,
                                       c10::optional<at::Tensor> dropmask,
                                       at::Tensor Mout, at::Tensor g,
@@ -262,7 +332,10 @@ std::vector<at::Tensor> mwe_bwd_fused(at::Tensor dY,
               "mwe_bwd_fused expects 2-d tensors");
   long T = dY.size(0);
   int W = (int)dY.size(1);
-  TORCH_CHECK(W == 96 || W == 128, "mwe_bwd_fused supports W in {96,128}");
+  TORCH_CHECK(W == 96 || W == 128 || W == 256,
+              "mwe_bwd_fused supports W in {96,128,256}");
+  TORCH_CHECK(!(compact && W == 256),
+              "mwe_bwd_fused: compact=True is not available at W = 256");
   TORCH_CHECK(T % 64 == 0, "mwe_bwd_fused needs T % 64 == 0 (TokenBatch pads)");
   TORCH_CHECK(weight.size(0) == 3 * W && weight.size(1) == 3 * W,
               "weight must be [3W,3W]");
@@ -298,7 +371,10 @@ std::vector<at::Tensor> mwe_bwd_fused(at::Tensor dY,
   const int ncols = 5 * W;
   long n = (T + 127) / 128;
   auto part = at::empty({n, (long)ncols}, f32);
-  if (W == 96 && compact)
+  if (W == 256)
+    launch_mwe_wide_bwd_fused(dY, dropmask, Mout, g, mu, rstd, which, WT, starts,
+                              ends, dPre, dX, part, T, stream);
+  else if (W == 96 && compact)
     launch_mwe_bwd_fused<96, true>(dY, dropmask, Mout, g, mu, rstd, which, WT,
                                    starts, ends, dPre, dX, part, T, stream);
   else if (W == 96)

@@ -740,6 +740,75 @@ def bench_mwe_dw():
           f"{float(c.abs().max()):.3e}")
 
 
+def bench_mwe_wide():
+    """One MWE block at W = 256 (srx_mwe_wide.hip.h), forward and backward
+    including dW, fused (ops.mwe_layer) against the composed route of
+    MaxoutWindowEncoder (seq2col -> linear_cdw -> maxout -> layernorm ->
+    F.dropout -> residual and its autograd backward) on the same inputs, docs
+    of 20 tokens, dropout 0.1.  T = 256K and, if memory allows, 1M.  The two
+    routes alternate in one loop; median / min / max of 30 event-timed calls
+    after 10 warm-ups, so the spread of each route is on its line."""
+    from spacy_ray_amd.ops import api as ops
+
+    W = 256
+    bf = torch.bfloat16
+    for T in (1 << 18, 1 << 20):
+        try:
+            X = (torch.randn(T, W, device=dev) * 0.5).to(bf).requires_grad_(True)
+            Wt = (torch.randn(3 * W, 3 * W, device=dev) / (3 * W) ** 0.5).to(bf) \
+                .requires_grad_(True)
+            bias = torch.zeros(3 * W, device=dev, dtype=bf, requires_grad=True)
+            g = torch.ones(W, device=dev, dtype=bf, requires_grad=True)
+            b = torch.zeros(W, device=dev, dtype=bf, requires_grad=True)
+            lens = torch.full((T // 20 + 1,), 20, device=dev, dtype=torch.long)
+            lens[-1] = T - 20 * (T // 20)
+            starts, ends = ops.boundary_masks_u8(lens, T)
+            mask = ops.dropout_mask_like(torch.empty(T, W, device=dev, dtype=bf), 0.1)
+            dY = torch.randn(T, W, device=dev).to(bf)
+            leaves = (X, Wt, bias, g, b)
+
+            def fused():
+                return ops.mwe_layer(X, Wt, bias, g, b, starts, ends, mask, 1e-5)
+
+            def composed():
+                Y = ops.linear_cdw(ops.seq2col(X, lens, starts, ends), Wt, bias)
+                Y = ops.layernorm(ops.maxout(Y.view(T, 3, W)), g, b, 1e-5)
+                return X + torch.nn.functional.dropout(Y, 0.1)
+
+            def timed(fn):
+                e0 = torch.cuda.Event(enable_timing=True)
+                e1 = torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = fn()
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1), out
+
+            ts = {(n, d): [] for n in ("fused", "composed")
+                  for d in ("fwd", "bwd+dW", "total")}
+            for it in range(40):
+                for name, fn in (("fused", fused), ("composed", composed)):
+                    t_f, Y = timed(fn)
+                    t_b, _ = timed(lambda: torch.autograd.grad(Y, leaves, dY))
+                    del Y
+                    if it >= 10:
+                        ts[name, "fwd"].append(t_f)
+                        ts[name, "bwd+dW"].append(t_b)
+                        ts[name, "total"].append(t_f + t_b)
+        except torch.OutOfMemoryError:
+            print(f"  mwe_wide T={T}: out of memory, skipped")
+            continue
+        flops = 2.0 * T * (3 * W) * (3 * W)
+        for d in ("fwd", "bwd+dW", "total"):
+            for name in ("fused", "composed"):
+                v = sorted(ts[name, d])
+                med = v[len(v) // 2]
+                nf = {"fwd": 1, "bwd+dW": 2, "total": 3}[d]
+                print(f"  mwe_wide T={T} {d:6s} {name:9s} median {med:8.3f} ms  "
+                      f"min {v[0]:8.3f}  max {v[-1]:8.3f}  "
+                      f"{nf * flops / med / 1e9:7.1f} TFLOP/s")
+
+
 def _alternate(fns, iters=30, warmup=10):
     """Median (and min) per-call GPU time of each fn, the fns alternating in
     one loop so that clock and cache state are shared."""
@@ -1039,7 +1108,7 @@ def bench_char_embed():
 
 
 ALL = {"mwe": bench_mwe, "sparse_linear": bench_sparse_linear, "dpre": bench_dpre, "ce": bench_ce, "mixer": bench_mixer,
-       "mwe_dw": bench_mwe_dw,
+       "mwe_dw": bench_mwe_dw, "mwe_wide": bench_mwe_wide,
        "floret": bench_floret, "vecloss": bench_vecloss,
        "most_similar": bench_most_similar, "span_pool": bench_span_pool, "attention_pool": bench_attention_pool,
        "gpustate": bench_gpustate, "attn": bench_attn,
