@@ -1823,10 +1823,11 @@ class _ReduceRagged(torch.autograd.Function):
             return dX, None, None
         (lengths,) = ctx.saved_tensors
         if mode == 2:
-            dX = dY.new_zeros(T, dY.shape[1])
+            # an empty doc (argmax -1) sends no gradient: row T is its sink
+            dX = dY.new_zeros(T + 1, dY.shape[1])
             which = ctx.argmax_cpu
-            dX.scatter_(0, which, dY)
-            return dX, None, None
+            dX.scatter_(0, torch.where(which >= 0, which, T), dY)
+            return dX[:T], None, None
         seg = torch.repeat_interleave(
             torch.arange(lengths.shape[0], device=dY.device), lengths.long()
         )

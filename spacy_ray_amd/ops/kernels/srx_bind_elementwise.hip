@@ -160,7 +160,10 @@ std::vector<at::Tensor> layernorm_bwd(at::Tensor dY, at::Tensor X, at::Tensor g,
   int W = (int)X.size(-1);
   long N = X.numel() / W;
   auto dX = at::empty_like(X);
-  auto acc_dt = deterministic ? at::kLong : at::kFloat;
+  // fp32 rows sum dg/db by fp64 atomics: fp32 adds in arrival order over
+  // thousands of waves would cost the fp32 result several digits
+  auto acc_dt = deterministic ? at::kLong
+                : X.scalar_type() == at::kFloat ? at::kDouble : at::kFloat;
   auto dg32 = at::zeros({W}, X.options().dtype(acc_dt));
   auto db32 = at::zeros({W}, X.options().dtype(acc_dt));
   auto stream = at::cuda::getCurrentCUDAStream();
@@ -236,8 +239,9 @@ void adam_step(at::Tensor grad, at::Tensor master, at::Tensor m, at::Tensor v,
                        0, stream, (const scalar_t*)grad.data_ptr(),
                        master.data_ptr<float>(), m.data_ptr<float>(),
                        v.data_ptr<float>(), (scalar_t*)param_out.data_ptr(), n,
-                       scale_ptr, (float)lr, (float)beta1, (float)beta2,
-                       (float)eps, (float)wd, (float)bc1, (float)bc2);
+                       scale_ptr, (float)(1.0 - lr * wd), (float)(lr / bc1),
+                       (float)beta1, (float)beta2, (float)(1.0 - beta1),
+                       (float)(1.0 - beta2), (float)eps, (float)bc2);
   });
 }
 
@@ -347,17 +351,17 @@ std::vector<at::Tensor> softmax_ce(at::Tensor scores, at::Tensor gold) {
   long N = scores.size(0);
   int C = (int)scores.size(1);
   auto dScores = at::empty_like(scores);
-  auto loss = at::zeros({2}, scores.options().dtype(at::kFloat));
-  if (N == 0) return {loss, dScores};
+  auto loss = at::zeros({2}, scores.options().dtype(at::kDouble));
+  if (N == 0) return {loss.to(at::kFloat), dScores};
   auto stream = at::cuda::getCurrentCUDAStream();
   int grid = (int)std::min<long>((N + 3) / 4, 2048);
   DISPATCH_F(scores.scalar_type(), {
     hipLaunchKernelGGL((softmax_ce_kernel<scalar_t>), dim3(grid), dim3(kBlock), 0,
                        stream, (const scalar_t*)scores.data_ptr(),
                        gold.data_ptr<int64_t>(), (scalar_t*)dScores.data_ptr(),
-                       loss.data_ptr<float>(), N, C);
+                       loss.data_ptr<double>(), N, C);
   });
-  return {loss, dScores};
+  return {loss.to(at::kFloat), dScores};
 }
 
 // ---------------------------------------------- segmented reductions

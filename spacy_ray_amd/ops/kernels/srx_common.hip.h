@@ -133,6 +133,12 @@ __device__ __forceinline__ float wave_reduce_sum(float v) {
   return v;
 }
 
+__device__ __forceinline__ double wave_reduce_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, SRX_WAVE);
+  return v;
+}
+
 // ---- deterministic accumulation (SRX_DETERMINISTIC / SURVEY §5.2)
 // Float atomics make gradient sums depend on scheduling order (fp add is
 // not associative).  The deterministic variants accumulate in FIXED-POINT
@@ -150,6 +156,18 @@ __device__ __forceinline__ void srx_atomic_add(void* buf, long idx, float v) {
     atomicAdd((unsigned long long*)buf + idx, (unsigned long long)q);
   } else {
     atomicAdd((float*)buf + idx, v);
+  }
+}
+
+// dg/db accumulation of the layernorm backward for element type T: the
+// fixed-point buffer when DET, else fp64 atomics for fp32 rows (the buffer
+// is then double) and fp32 atomics for 16-bit rows
+template <typename T, bool DET>
+__device__ __forceinline__ void srx_ln_acc_add(void* buf, long idx, float v) {
+  if (!DET && sizeof(T) == 4) {
+    atomicAdd((double*)buf + idx, (double)v);
+  } else {
+    srx_atomic_add<DET>(buf, idx, v);
   }
 }
 

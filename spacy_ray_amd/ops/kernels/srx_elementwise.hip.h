@@ -161,16 +161,34 @@ __global__ void layernorm_fwd_kernel(const T* __restrict__ X,
   const long nwaves = ((long)gridDim.x * blockDim.x) / SRX_WAVE;
   for (long n = wave; n < N; n += nwaves) {
     const T* row = X + n * (long)W;
-    float s = 0.f, sq = 0.f;
-    for (int w = lane; w < W; w += SRX_WAVE) {
-      float v = Elem<T>::ld(row + w);
-      s += v;
-      sq += v * v;
+    float mu, var;
+    if constexpr (sizeof(T) == 4) {
+      // fp32: the row sum in fp64 (an fp32 sum of W values rounds at the
+      // spacing of the partial sums, several ulp of mu), then the variance
+      // about the mean: E[x^2] - mu^2 cancels once |mu| >> std (20x the
+      // error of this form at mean 8, 350x at mean 100)
+      double s = 0.0;
+      for (int w = lane; w < W; w += SRX_WAVE) s += (double)Elem<T>::ld(row + w);
+      mu = (float)(wave_reduce_sum(s) / W);
+      float ss = 0.f;
+      for (int w = lane; w < W; w += SRX_WAVE) {
+        float d = Elem<T>::ld(row + w) - mu;
+        ss += d * d;
+      }
+      var = wave_reduce_sum(ss) / W;
+    } else {
+      // bf16: the output rounding hides the one-pass cancellation
+      float s = 0.f, sq = 0.f;
+      for (int w = lane; w < W; w += SRX_WAVE) {
+        float v = Elem<T>::ld(row + w);
+        s += v;
+        sq += v * v;
+      }
+      s = wave_reduce_sum(s);
+      sq = wave_reduce_sum(sq);
+      mu = s / W;
+      var = sq / W - mu * mu;
     }
-    s = wave_reduce_sum(s);
-    sq = wave_reduce_sum(sq);
-    float mu = s / W;
-    float var = sq / W - mu * mu;
     float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
     if (lane == 0) {
       mu_out[n] = mu;
@@ -203,17 +221,36 @@ __global__ void layernorm_fwd_v2_kernel(const T* __restrict__ X,
   const int npairs = W / 2;
   for (long n = wave; n < N; n += nwaves) {
     const T* row = X + n * (long)W;
-    float s = 0.f, sq = 0.f;
-    for (int p = lane; p < npairs; p += SRX_WAVE) {
-      float v[2];
-      Elem2<T>::ld(row + 2 * p, v);
-      s += v[0] + v[1];
-      sq += v[0] * v[0] + v[1] * v[1];
+    float mu, var;
+    if constexpr (sizeof(T) == 4) {  // fp32: fp64 row sum, two passes, as above
+      double s = 0.0;
+      for (int p = lane; p < npairs; p += SRX_WAVE) {
+        float v[2];
+        Elem2<T>::ld(row + 2 * p, v);
+        s += (double)v[0] + (double)v[1];
+      }
+      mu = (float)(wave_reduce_sum(s) / W);
+      float ss = 0.f;
+      for (int p = lane; p < npairs; p += SRX_WAVE) {
+        float v[2];
+        Elem2<T>::ld(row + 2 * p, v);
+        float d0 = v[0] - mu, d1 = v[1] - mu;
+        ss += d0 * d0 + d1 * d1;
+      }
+      var = wave_reduce_sum(ss) / W;
+    } else {
+      float s = 0.f, sq = 0.f;
+      for (int p = lane; p < npairs; p += SRX_WAVE) {
+        float v[2];
+        Elem2<T>::ld(row + 2 * p, v);
+        s += v[0] + v[1];
+        sq += v[0] * v[0] + v[1] * v[1];
+      }
+      s = wave_reduce_sum(s);
+      sq = wave_reduce_sum(sq);
+      mu = s / W;
+      var = sq / W - mu * mu;
     }
-    s = wave_reduce_sum(s);
-    sq = wave_reduce_sum(sq);
-    float mu = s / W;
-    float var = sq / W - mu * mu;
     float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
     if (lane == 0) {
       mu_out[n] = mu;
@@ -296,8 +333,8 @@ __global__ void layernorm_bwd_v2_kernel(const T* __restrict__ dY,
 #pragma unroll
     for (int e = 0; e < 2; e++) {
       int w = 2 * p + e;
-      if (dg_loc[2 * c + e] != 0.f) srx_atomic_add<DET>(dg32, w, dg_loc[2 * c + e]);
-      if (db_loc[2 * c + e] != 0.f) srx_atomic_add<DET>(db32, w, db_loc[2 * c + e]);
+      if (dg_loc[2 * c + e] != 0.f) srx_ln_acc_add<T, DET>(dg32, w, dg_loc[2 * c + e]);
+      if (db_loc[2 * c + e] != 0.f) srx_ln_acc_add<T, DET>(db32, w, db_loc[2 * c + e]);
     }
   }
 }
@@ -306,7 +343,8 @@ __global__ void layernorm_bwd_v2_kernel(const T* __restrict__ dY,
 // rows, ONE atomicAdd per column per wave at the end.  (A per-row-per-elem
 // atomic version serialized on the 2*W hot addresses: 772 us/call at
 // N=32k, W=96 — this shape runs in ~30 us.)  Needs W <= SRX_LN_MAX_W.
-// DET=true: dg/db buffers are int64 fixed-point (bit-deterministic).
+// DET=true: dg/db buffers are int64 fixed-point (bit-deterministic);
+// otherwise double for fp32 rows and float for bf16 (srx_ln_acc_add).
 template <typename T, bool DET = false>
 __global__ void layernorm_bwd_kernel(const T* __restrict__ dY,
                                      const T* __restrict__ X,
@@ -354,8 +392,8 @@ __global__ void layernorm_bwd_kernel(const T* __restrict__ dY,
   for (int c = 0; c < ncols; c++) {
     int w = lane + c * SRX_WAVE;
     if (w < W) {
-      srx_atomic_add<DET>(dg32, w, dg_loc[c]);
-      srx_atomic_add<DET>(db32, w, db_loc[c]);
+      srx_ln_acc_add<T, DET>(dg32, w, dg_loc[c]);
+      srx_ln_acc_add<T, DET>(db32, w, db_loc[c]);
     }
   }
 }
@@ -398,20 +436,22 @@ __global__ void adam_step_kernel(const T* __restrict__ grad,
                                  float* __restrict__ v,
                                  T* __restrict__ param_out,
                                  long n, const float* __restrict__ clip_scale_ptr,
-                                 float lr,
-                                 float beta1, float beta2, float eps,
-                                 float wd, float bc1, float bc2) {
+                                 float decay, float step,
+                                 float beta1, float beta2, float omb1,
+                                 float omb2, float eps, float bc2) {
   const float clip_scale = clip_scale_ptr ? *clip_scale_ptr : 1.0f;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (long)gridDim.x * blockDim.x) {
     float gv = Elem<T>::ld(grad + i) * clip_scale;
-    float p = master[i] * (1.0f - lr * wd);
-    float mi = beta1 * m[i] + (1.0f - beta1) * gv;
-    float vi = beta2 * v[i] + (1.0f - beta2) * gv * gv;
+    // decay = 1 - lr wd, step = lr / bc1, omb = 1 - beta: rounded once from
+    // the host's doubles (1.0f - 0.999f is off by a relative 4.7e-5)
+    float p = master[i] * decay;
+    float mi = beta1 * m[i] + omb1 * gv;
+    float vi = beta2 * v[i] + omb2 * gv * gv;
     m[i] = mi;
     v[i] = vi;
     float denom = sqrtf(vi / bc2) + eps;
-    p -= (lr / bc1) * (mi / denom);
+    p -= step * (mi / denom);
     master[i] = p;
     Elem<T>::st(param_out + i, p);
   }

@@ -6,12 +6,12 @@
 // ------------------------------------------------------- softmax + CE
 // One wave per row (grid-stride): out d[n,c] = softmax(scores[n]) - onehot,
 // 0 for ignored rows (gold < 0); per-wave loss partials -> one atomicAdd
-// per wave into loss_out[0]; n_valid counted into loss_out[1].
+// per wave into loss_out[0] (fp64); n_valid counted into loss_out[1].
 template <typename T>
 __global__ void softmax_ce_kernel(const T* __restrict__ scores,
                                   const int64_t* __restrict__ gold,
                                   T* __restrict__ dScores,
-                                  float* __restrict__ loss_out,
+                                  double* __restrict__ loss_out,
                                   long N, int C) {
   const int lane = threadIdx.x & (SRX_WAVE - 1);
   const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) / SRX_WAVE;
@@ -33,19 +33,25 @@ __global__ void softmax_ce_kernel(const T* __restrict__ scores,
     float z = 0.f;
     for (int c = lane; c < C; c += SRX_WAVE) z += __expf(Elem<T>::ld(row + c) - m);
     z = wave_reduce_sum(z);
-    float logz = __logf(z) + m;
+    // p = exp(x - m) / z and loss = log z - (x_g - m): x - m is exact for
+    // nearby logits, while x - (log z + m) rounds at the spacing of |m| and
+    // costs p a relative |m| * 2^-24 (40 ulp at logits near 100)
+    float inv_z = 1.f / z;
     for (int c = lane; c < C; c += SRX_WAVE) {
-      float p = __expf(Elem<T>::ld(row + c) - logz);
+      float p = __expf(Elem<T>::ld(row + c) - m) * inv_z;
       Elem<T>::st(drow + c, p - (c == (int)g ? 1.f : 0.f));
     }
     if (lane == 0) {
-      loss_acc += logz - Elem<T>::ld(row + (int)g);
+      loss_acc += __logf(z) - (Elem<T>::ld(row + (int)g) - m);
       count_acc += 1.f;
     }
   }
-  if (lane == 0 && loss_acc != 0.f) {
-    atomicAdd(loss_out + 0, loss_acc);
-    atomicAdd(loss_out + 1, count_acc);
+  // a confidently-right row has an fp32 loss of exactly 0 and still counts
+  // fp64 atomics: thousands of fp32 adds in arrival order lose more of the
+  // summed loss than a tree sum does; the caller rounds to fp32 once
+  if (lane == 0 && (loss_acc != 0.f || count_acc != 0.f)) {
+    atomicAdd(loss_out + 0, (double)loss_acc);
+    atomicAdd(loss_out + 1, (double)count_acc);
   }
 }
 
@@ -159,7 +165,7 @@ __global__ void reduce_ragged_kernel(const T* __restrict__ X,
     int32_t s = offsets[d], e = offsets[d + 1];
     for (int w = lane; w < W; w += SRX_WAVE) {
       float acc = MODE == 2 ? -1e38f : 0.f;
-      int32_t arg = s;
+      int32_t arg = e > s ? s : -1;  // empty doc: pooled row 0, no argmax
       for (int32_t t = s; t < e; t++) {
         float v = Elem<T>::ld(X + t * (long)W + w);
         if (MODE == 2) {
@@ -205,10 +211,12 @@ __global__ void reduce_max_bwd_kernel(const T* __restrict__ dY,
   const long total = N * (long)W;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (long)gridDim.x * blockDim.x) {
-    long d = i / W;
     int w = (int)(i % W);
+    // dX zero-initialized by caller; argmax positions are unique per (d,w);
+    // an empty doc stores -1 and sends no gradient
+    int32_t a = argmax[i];
+    if (a < 0) continue;
     float v = Elem<T>::ld(dY + i);
-    // dX zero-initialized by caller; argmax positions are unique per (d,w)
-    Elem<T>::st(dX + argmax[i] * (long)W + w, v);
+    Elem<T>::st(dX + a * (long)W + w, v);
   }
 }

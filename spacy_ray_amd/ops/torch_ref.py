@@ -412,9 +412,11 @@ def reduce_mean_ragged(X: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
 
 
 def reduce_max_ragged(X: torch.Tensor, lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(max [N, W], argmax row [N, W]).  An empty doc pools to a zero row, as
+    in sum and mean, and its argmax is -1: it takes and sends no gradient."""
     n_docs = lengths.shape[0]
-    out = X.new_full((n_docs, X.shape[1]), float("-inf"))
-    which = torch.zeros(n_docs, X.shape[1], dtype=torch.long, device=X.device)
+    out = X.new_zeros(n_docs, X.shape[1])
+    which = torch.full((n_docs, X.shape[1]), -1, dtype=torch.long, device=X.device)
     off = 0
     for i, n in enumerate(lengths.tolist()):
         if n:

@@ -121,6 +121,40 @@ def test_ragged_reductions():
     assert torch.allclose(mx[2], X[3:].max(dim=0).values)
 
 
+@pytest.mark.parametrize("lengths_l", [[0, 4, 0, 0, 2], [4, 2, 0], [0], [3, 1, 7, 5]],
+                         ids=str)
+def test_ragged_max_empty_docs_cpu(lengths_l):
+    """The CPU path of the ragged max: an empty document pools to a zero
+    row, has argmax -1, and neither takes nor sends a gradient."""
+    import ref64
+
+    lengths = torch.tensor(lengths_l)
+    T, W, N = sum(lengths_l), 5, len(lengths_l)
+    X = ref64.ragged_inputs(lengths_l, W, torch.float32).double()
+    dY = torch.randn(N, W, dtype=torch.float64,
+                     generator=torch.Generator().manual_seed(1))
+    want, wargmax = ref64.reduce_ragged64(X, lengths, 2)
+    wdX = ref64.reduce_ragged_bwd64(dY, lengths, 2, T, wargmax)
+    empty = lengths == 0
+
+    out, which = ref.reduce_max_ragged(X, lengths)
+    assert torch.equal(out, want) and torch.equal(which, wargmax)
+    assert not out[empty].any() and bool((which[empty] == -1).all())
+
+    x = X.clone().requires_grad_(True)
+    pooled = ops.reduce_max_ragged(x, lengths)
+    assert torch.equal(pooled.detach(), want)
+    pooled.backward(dY)
+    assert x.grad.shape == X.shape and torch.equal(x.grad, wdX)
+    if T:
+        # were an empty doc's dY scattered anywhere, a change to it would show
+        x2 = X.clone().requires_grad_(True)
+        dY2 = dY.clone()
+        dY2[empty] += 100.0
+        ops.reduce_max_ragged(x2, lengths).backward(dY2)
+        assert torch.equal(x2.grad, x.grad)
+
+
 def test_activations_match_torch_builtins():
     """mish/swish/gelu equal torch's own implementations; clipped_linear
     family obeys its closed form (Thinc kernel-surface parity)."""
